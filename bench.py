@@ -15,7 +15,13 @@ Reported next to it in the same JSON line (never part of `value`):
   burgers  : (--workload burgers / burgers-bf16 make it the main line instead) the Burgers base model's train / sample step;
   roofline : the dominant convolution kernel of the main workload; cpu_baseline: the oracle on the host cores.
 
+A plain run measures the main line only: set up, warm up, time --steps steps, print the line (roofline / cpu_baseline null). --full adds
+everything else above (the side legs, the profiled extra step behind `roofline`, the CPU baseline; --no-extras / --no-cpu-baseline /
+--max-seconds trim it). --dump-outputs DIR writes what the last timed step handed its caller as .npy files (dump_outputs);
+with the same arguments the inputs, weights and random draws are the same in every run.
+
     python bench.py --gpus 1 --steps 100 --warmup 5
+    python bench.py --gpus 1 --steps 100 --warmup 5 --full
     python bench.py --gpus N ...          (no launcher: re-executes itself as N ranks under torch.distributed.run on a free port)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -832,6 +838,26 @@ def conv_roofline(ts_step, ops):
             'conv_ms_per_step': {k: round(v[0], 3) for k, v in agg.items()}}
 
 
+def dump_outputs(out_dir, ts, loss, gnorm, n_sample=1 << 20):
+    """--dump-outputs: what the last timed training step handed its caller, as float32 .npy files in out_dir: the loss, the pre-clip global
+    gradient norm, and the same seeded sample of n_sample positions (sample_index.npy, float64) of the updated parameters, their gradients and
+    the EMA weights, all three flat in model.parameters() order (the flat buffers of wdno_amd.trainer.FlatBuffers). Every parameter is
+    written when there are no more than n_sample of them."""
+    import numpy as np
+    buf = ts.opt.buf
+    torch.cuda.synchronize()
+    n = buf.flat_param.numel()
+    idx = np.arange(n) if n <= n_sample else np.sort(np.random.default_rng(0).choice(n, size=n_sample, replace=False))
+    it = torch.from_numpy(idx).to(buf.flat_param.device)
+    arrays = {'loss': loss.reshape(()), 'grad_norm': gnorm.reshape(()), 'params_sample': buf.flat_param[it], 'grads_sample': buf.flat_grad[it]}
+    if ts.ema is not None:
+        arrays['ema_sample'] = ts.ema.flat[it]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, 'sample_index.npy'), idx.astype(np.float64))
+
+
 def _rccl_version():
     try:
         return list(torch.cuda.nccl.version())
@@ -869,7 +895,12 @@ def main():
     ap.add_argument('--burgers-grid', default='64x64', help="tensor size of the Burgers workloads: 64x64 (reference-native) or 80x64 (north-star synthetic: fields [B,2,160,128] through the HIP DWT)")
     ap.add_argument('--max-seconds', type=float, default=float(os.environ.get('WDNO_BENCH_MAX_SECONDS', '1500')),
                     help='wall-clock guard for the whole run: a SIDE leg is skipped (and named in `skipped_legs`) when its budgeted cost no longer fits; the main line is never dropped')
+    ap.add_argument('--full', action='store_true', help='also run the side legs, the profiled extra step behind `roofline` and the CPU baseline (off: the main line only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="write the last timed step's loss, gradient norm and a seeded sample of the "
+                    'updated parameters, gradients and EMA weights as DIR/<name>.npy (float32; the sample index float64)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     t_run0 = time.perf_counter()
 
     if args.gpus > 1 and 'RANK' not in os.environ:
@@ -949,15 +980,17 @@ def main():
         elapsed = max(float(v[0]) for v in allv)
         per_rank = {'ms_per_step': [round(float(v[1]), 3) for v in allv], 'exposed_allreduce_ms': [round(float(v[2]), 3) for v in allv]}
     final_loss = float(losses[-1]) if losses else float('nan')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts, loss, gn)          # before any extra step below moves the parameters on
 
     extras = {}
     roofline = cpu = None
     cap, ts._cap = getattr(ts, '_cap', None), None          # the profiled extra step runs launch by launch (HIP events around every convolution)
-    if rank != 0 and world > 1:
+    if args.full and rank != 0 and world > 1:
         ts.step(x)              # rank 0's profiled extra step below contains the gradient all-reduce: every rank has to take part in it
-    if rank == 0:
+    if args.full and rank == 0:
         roofline = conv_roofline(lambda: ts.step(x), ops)
-    run_multi_side = world > 1 and smoke and not args.no_extras
+    run_multi_side = args.full and world > 1 and smoke and not args.no_extras
     if run_multi_side:
         # every rank has to take the same decision (the legs end in an all_gather): rank 0's clock decides, broadcast to all
         flag = torch.tensor([1.0 if (time.perf_counter() - t_run0) + 150 <= args.max_seconds else 0.0], device=device)
@@ -1005,7 +1038,7 @@ def main():
         if not ok:
             skipped.append({'leg': name, 'budgeted_s': cost_s, 'elapsed_s': round(time.perf_counter() - t_run0, 1)})
         return ok
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_extras:
             try:
                 if smoke:
@@ -1110,7 +1143,7 @@ def main():
                                           'devices_visible': torch.cuda.device_count()} if world > 1 else None)},
             'samples_per_sec': round(world * args.steps * batch / elapsed, 3),
             'final_loss': final_loss,
-            'roofline': roofline, 'step_roofline': step_roofline, 'cpu_baseline': cpu,
+            'roofline': roofline, 'step_roofline': step_roofline, 'cpu_baseline': cpu, 'full': args.full,
         }
         if 'sampling' in extras:
             out['ddpm_sample_steps_per_sec'] = (extras['sampling']['graph_steps_per_sec_global'] if world > 1 else

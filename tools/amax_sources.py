@@ -59,7 +59,7 @@ for fn in ('split_f16', 'split_f16_colsum'):
     setattr(ops, fn, mk2(o))
 
 import bench
-sys.argv = ['bench.py', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--sample-steps', '0']
+sys.argv = ['bench.py', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--sample-steps', '0', '--full']
 bench.main()
 tot = sum(v[1] for v in stats.values())
 for k, v in sorted(stats.items(), key=lambda kv: -kv[1][1]):

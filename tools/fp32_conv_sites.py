@@ -19,7 +19,7 @@ def traw(x, wt, bias_p, cout_p):
     return ot(x, wt, bias_p, cout_p)
 ops.conv_transpose_raw = traw
 import bench
-sys.argv = ['bench.py', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--sample-steps', '0']
+sys.argv = ['bench.py', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--sample-steps', '0', '--full']
 bench.main()
 for k, v in sorted(stats.items(), key=lambda kv: -kv[1]):
     print(v, k)

@@ -34,5 +34,5 @@ ls -la $O
 python $R/tools/timeline_gaps.py $(find /tmp/prof_smoke -name "*.db" | head -1) $O/smoke_timeline.md 0.3
 run_stats burgers_80x64_b16 python $R/bench.py --workload burgers --burgers-grid 80x64 --steps 6 --warmup 1 --no-cpu-baseline --no-extras; echo "b16 80x64 stats $(( $(date +%s) - t0 ))s"
 python $R/tools/parity_report.py --out $O/parity_report.json > $O/parity_report.log 2>&1; echo "parity $(( $(date +%s) - t0 ))s"
-python $R/bench.py --steps 100 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "bench $(( $(date +%s) - t0 ))s"
+python $R/bench.py --full --steps 100 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "bench $(( $(date +%s) - t0 ))s"
 ls -la $O

@@ -35,6 +35,6 @@ run_stats burgers_bf16 python $R/bench.py --workload burgers-bf16 --steps 3 --wa
 run_stats burgers_b16 python $R/bench.py --workload burgers --steps 6 --warmup 1 --no-cpu-baseline --no-extras; echo "b16 stats $(( $(date +%s) - t0 ))s"
 run_stats smoke_bf16 python $R/bench.py --workload smoke-bf16 --steps 4 --warmup 1 --no-cpu-baseline --no-extras; echo "smoke bf16 stats $(( $(date +%s) - t0 ))s"
 python $R/tools/parity_report.py --out $O/parity_report.json > $O/parity_report.log 2>&1; echo "parity $(( $(date +%s) - t0 ))s"
-python $R/bench.py --steps 100 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "bench $(( $(date +%s) - t0 ))s"
+python $R/bench.py --full --steps 100 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "bench $(( $(date +%s) - t0 ))s"
 fi
 ls -la $O
