@@ -581,6 +581,25 @@ int wdno_gather_items(const void* table, int n_items, int blocks_per_item, wdno_
 /* ema = ema*beta + p*(1-beta)  (ema_pytorch lerp) */
 int wdno_ema_update(float* ema, const float* p, int64_t n, float beta, wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ Burgers solver
+ * burgers_numeric_solve_free (burgers/ddpm_burgers/generate_burgers.py:104-204): the finite-difference solver that scores a designed control
+ * (eval_ddpm_burgers.py:203, test_util.py:75,77). u0 [N][nx0] and f [N][nt_f][nxf] are linearly interpolated to s points (l.131-132, torch's
+ * align_corners = False rule), then `steps` explicit-Euler steps of u_i += dt (-(1/2) c (u_{i+1}^2 - u_{i-1}^2) + d (u_{i-1} + u_{i+1}) +
+ * dm u_i + f[j / f_time]_i) on s interior points with zero ghosts (l.176-186, each point in the reference's operation order, fp32).
+ * out [N][num_t + 1][out_cols]: row 0 = the interpolated u0, row r = the state after step r * record_time - 1 (l.191-195), columns
+ * 0, sub_s, 2 sub_s, ... (l.200-201; sub_s = 1 without the down-sampling). One launch; one workgroup of `waves` waves per trajectory, each lane
+ * holding `points` grid points: waves in {1, 2, 4, 8, 16}, points in {2, 4, 8, 16, 32} (32 only up to 8 waves), 64 waves points >= s.
+ * The host computes the integers (l.138-148) and raises the reference's exceptions; WDNO_EINVAL when they are not consistent
+ * (f index or record counter past its end). Constants: c = fp32(1 / (2 dx)), d = fp32(visc / dx^2), dm = fp32(-2 visc / dx^2), dx = 1 / (s + 1),
+ * dt = fp32(dt) (l.163-165). The result of a trajectory does not depend on (waves, points), N or its index. */
+typedef struct {
+  int N, s, nx0, nt_f, nxf;
+  int steps, record_time, f_time, num_t, sub_s, out_cols;
+  int waves, points;
+  float c, d, dm, dt;
+} wdno_burgers_desc;
+int wdno_burgers_solve(const float* u0, const float* f, float* out, const wdno_burgers_desc* d, wdno_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,11 @@ class RowsSumItem(C.Structure):              # include/wdno_hip.h: wdno_rows_sum
     _fields_ = [('part', C.c_void_p), ('out', C.c_void_p), ('rows', I), ('stride', I), ('col0', I), ('ncols', I), ('is_double', I), ('reserved', I)]
 
 
+class BurgersDesc(C.Structure):             # include/wdno_hip.h: wdno_burgers_desc
+    _fields_ = [(k, I) for k in ('N', 's', 'nx0', 'nt_f', 'nxf', 'steps', 'record_time', 'f_time', 'num_t', 'sub_s', 'out_cols', 'waves',
+                                 'points')] + [(k, F) for k in ('c', 'd', 'dm', 'dt')]
+
+
 PD, PG, PA, PC = C.POINTER(DwtDesc), C.POINTER(ConvGeom), C.POINTER(AttnDesc), C.POINTER(CondDesc)
 PF = C.POINTER(C.c_float)
 
@@ -176,6 +181,7 @@ PROTOTYPES = {
     'wdno_gather_items': (I, [P, I, I, P]),
     'wdno_relpos_bias_fwd': (I, [P, P, P, I, I, P]),
     'wdno_relpos_bias_bwd': (I, [P, P, P, I, I, I, P]),
+    'wdno_burgers_solve': (I, [P, P, P, C.POINTER(BurgersDesc), P]),
 }
 
 _lib = None
