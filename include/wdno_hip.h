@@ -35,7 +35,8 @@ const char* wdno_strerror(int code);
 int wdno_version(void);
 /* last hip error string seen by the library on this thread (diagnostics only) */
 const char* wdno_last_hip_error(void);
-/* diagnostics only: ablation switches of the convolution kernels (0 = off) */
+/* diagnostics only: the library-wide debug mode (0 = production). One integer that switches kernel selection for A/B measurements and tests;
+ * wdno_amd/csrc/debug_modes.h lists every value. WDNO_EINVAL, and the mode stays as it was, for a value that is not listed there. */
 int wdno_set_debug(int mode);
 
 /* ------------------------------------------------------------------------------------------------ wavelets

@@ -21,6 +21,7 @@ from tests.helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
+DBG_REG_STAGED_CONV = 5        # library debug mode (wdno_amd/csrc/debug_modes.h): never the LDS-DMA convolution kernels
 
 
 @pytest.fixture()
@@ -65,10 +66,10 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize('mode', [0, 5], ids=['default', 'register_staged'])
+@pytest.mark.parametrize('mode', [0, DBG_REG_STAGED_CONV], ids=['default', 'register_staged'])
 @pytest.mark.parametrize('name,xs,ws,stride,padding', CASES, ids=[c[0] for c in CASES])
 def test_bf16_conv_equals_exact_product_of_rounded_operands(ops, name, xs, ws, stride, padding, mode):
-    if mode == 5 and name == '2d_3x3_1024':
+    if mode == DBG_REG_STAGED_CONV and name == '2d_3x3_1024':
         pytest.skip('one kernel family is enough for the largest case')
     nd = len(ws) - 2
     seed = sum(name.encode()) % 1000
@@ -88,18 +89,16 @@ def test_bf16_conv_equals_exact_product_of_rounded_operands(ops, name, xs, ws, s
     xd[..., :xs[1]] = to_cl(x)
     xd = xd.float().to(DEV).requires_grad_(True)
     wd, bd = w.float().to(DEV).requires_grad_(True), b.float().to(DEV).requires_grad_(True)
-    lib = ops._lib_()
-    lib.wdno_set_debug(mode)
     ops.PROFILE = {}
     try:
-        y = ops.conv_cl(xd, wd, bd, stride=stride, padding=padding)
-        god = torch.zeros(tuple(y.shape), dtype=torch.float64)
-        god[..., :ws[0]] = to_cl(go)
-        y.backward(god.float().to(DEV))
-        torch.cuda.synchronize()
+        with ops._lib.debug_mode(mode):
+            y = ops.conv_cl(xd, wd, bd, stride=stride, padding=padding)
+            god = torch.zeros(tuple(y.shape), dtype=torch.float64)
+            god[..., :ws[0]] = to_cl(go)
+            y.backward(god.float().to(DEV))
+            torch.cuda.synchronize()
     finally:
         used, ops.PROFILE = set(ops.PROFILE), None
-        lib.wdno_set_debug(0)
     assert any('h3' in k for k in used), used
     assert rel_l2(from_cl(y.detach().cpu())[:, :ws[0]], yr) < 2e-6, 'forward'
     # (the data gradient of the strided down-sampling convolution runs as four parity-class convolutions on the same bf16 operands)

@@ -9,22 +9,23 @@ import torch
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
+# library debug modes set below (wdno_amd/csrc/debug_modes.h is the list; tests/test_host.py checks these numbers against it)
+DBG_PER_AXIS_DWT = 11          # the per-axis passes instead of the fused transform
+DBG_DWT3_SYNTH_LDS = 45        # 3-D synthesis with all frames of a tile in LDS instead of the streaming kernel
 
 
 @pytest.fixture(scope='module')
 def W():
     from wdno_amd import wavelets, _lib
-    return wavelets, _lib.load()
+    _lib.load()
+    return wavelets, _lib
 
 
 def both(lib, fn):
     """fn() through the fused kernels (default) and through the per-axis passes (debug switch 11)."""
     a = fn()
-    lib.wdno_set_debug(11)
-    try:
+    with lib.debug_mode(DBG_PER_AXIS_DWT):
         b = fn()
-    finally:
-        lib.wdno_set_debug(0)
     torch.cuda.synchronize()
     return a, b
 
@@ -132,9 +133,6 @@ def test_streaming_3d_synthesis_equals_the_all_frames_kernel(W, mode, wave, shap
         (y * torch.cos(torch.arange(y.numel(), device=DEV, dtype=torch.float32)).reshape(y.shape)).sum().backward()
         return z.detach(), xx.grad
     a = run()
-    lib.wdno_set_debug(45)
-    try:
+    with lib.debug_mode(DBG_DWT3_SYNTH_LDS):
         b = run()
-    finally:
-        lib.wdno_set_debug(0)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])

@@ -15,6 +15,7 @@ from tests.helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
+DBG_STEM_EVERY_STAGE = 57       # library debug mode (wdno_amd/csrc/debug_modes.h): the stem ignores the zero-box hint
 
 
 @pytest.fixture()
@@ -66,24 +67,22 @@ def test_stem_skipping_zero_stages_is_bit_identical(ops, math, shape, box):
     gw = torch.Generator().manual_seed(5)
     wt = (torch.randn(64, c, 7, 7, 7, generator=gw) / (c * 343) ** 0.5).to(DEV)
     b = torch.randn(64, generator=gw).to(DEV)
-    lib = ops._lib_()
 
     def run(hint, debug):
         xi = x.clone()
         if hint:
             ops.set_zero_box(xi, box)
-        lib.wdno_set_debug(debug)
         ops.PROFILE = {}
         try:
-            y = ops.conv_cl(xi, wt, b, padding=3)
-            torch.cuda.synchronize()
+            with ops._lib.debug_mode(debug):
+                y = ops.conv_cl(xi, wt, b, padding=3)
+                torch.cuda.synchronize()
         finally:
             used, ops.PROFILE = set(ops.PROFILE), None
-            lib.wdno_set_debug(0)
         if not (math == 'bf16' and ((c + 7) // 8 * 8) % 16):      # (one bf16 plane is padded to 8 channels, not to whole 16-channel blocks: 82 -> 88 runs on the chunked kernel)
             assert any('h3t' in k for k in used), used
         return y
-    y_all, y_oob, y_box = run(False, 57), run(False, 0), run(True, 0)
+    y_all, y_oob, y_box = run(False, DBG_STEM_EVERY_STAGE), run(False, 0), run(True, 0)
     assert torch.equal(y_all, y_oob) and torch.equal(y_all, y_box)
     if math == 'f16x3':
         ref = F.conv3d(x[..., :c].permute(0, 4, 1, 2, 3).double().cpu(), wt.double().cpu(), b.double().cpu(), padding=3).permute(0, 2, 3, 4, 1)

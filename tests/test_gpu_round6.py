@@ -11,6 +11,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
+# library debug modes set below (wdno_amd/csrc/debug_modes.h is the list; tests/test_host.py checks these numbers against it)
+DBG_WGRAD_NO_SPLIT_PAIR = 70    # round 5's item plan of the window weight gradient
+DBG_STEM_TILES_256 = 72         # the 7-wide stem always on 256-pixel tiles
 
 
 @pytest.fixture(scope='module')
@@ -38,7 +41,6 @@ def test_split_pair_plan_equals_the_round5_plan(name, xs, ws, math):
     empty window): other split boundaries, so fp32 sums in another order -- equal to 1e-5 relative (measured ~1e-6), each plan bit-reproducible;
     and, through the two-step API (partial sums, then wdno_wgrad_reduce_multi), bit-identical to the one-call API."""
     from wdno_amd import ops, _lib
-    lib = ops._lib_()
     prev = ops.CONV_MATH
     ops.CONV_MATH = math
     try:
@@ -50,14 +52,11 @@ def test_split_pair_plan_equals_the_round5_plan(name, xs, ws, math):
         pd = tuple(v // 2 for v in ks)
         f = lambda: ops.conv_wgrad_h3(xpl, tuple(xs[:4]), ypl, tuple(xs[1:4]), ks, (1, 1, 1), pd, param_kc=(k, c))
         res = {}
-        for mode in (0, 70):
-            lib.wdno_set_debug(mode)
-            try:
+        for mode in (0, DBG_WGRAD_NO_SPLIT_PAIR):
+            with _lib.debug_mode(mode):
                 res[mode] = f().clone()
                 assert torch.equal(res[mode], f())
-            finally:
-                lib.wdno_set_debug(0)
-        rel = ((res[0] - res[70]).norm() / res[70].norm()).item()
+        rel = ((res[0] - res[DBG_WGRAD_NO_SPLIT_PAIR]).norm() / res[DBG_WGRAD_NO_SPLIT_PAIR].norm()).item()
         print(name, math, 'split-pair vs round-5 plan', rel)
         assert 0 < rel < 1e-5                               # the plans really differ (another split count), the sums agree
         dst = torch.full_like(res[0], float('nan'))
@@ -145,7 +144,6 @@ def test_stem_forward_on_192_pixel_tiles_equals_the_256_pixel_tiles(xs):
     256-pixel tiles: 192-pixel tiles (csrc/conv_h3t.hip, the batch-1 sampling step) -- every output element is the same chain of products in
     the same order, so the bits equal those of the 256-pixel tiles (library debug mode 72)."""
     from wdno_amd import ops
-    lib = ops._lib_()
     g = torch.Generator(device=DEV).manual_seed(11)
     x = torch.randn(*xs, 44, device=DEV, generator=g)
     x[..., 42:] = 0
@@ -153,17 +151,14 @@ def test_stem_forward_on_192_pixel_tiles_equals_the_256_pixel_tiles(xs):
     b = torch.randn(64, device=DEV, generator=g)
     res = {}
     with torch.no_grad():
-        for mode in (0, 72):
-            lib.wdno_set_debug(mode)
-            try:
+        for mode in (0, DBG_STEM_TILES_256):
+            with ops._lib.debug_mode(mode):
                 ops.PROFILE = {}
                 res[mode] = ops.conv_cl(x, w, b, stride=1, padding=3).clone()
                 names, ops.PROFILE = list(ops.PROFILE), None
-            finally:
-                lib.wdno_set_debug(0)
             if mode == 0 and xs[1] == 24:                    # (fewer than 100 tiles: the chunked kernel, both modes)
                 assert names == ['conv_fwd_h3t_kernel<192,64>'], names
-    assert torch.equal(res[0], res[72])
+    assert torch.equal(res[0], res[DBG_STEM_TILES_256])
     ref = torch.nn.functional.conv3d(x[..., :42].permute(0, 4, 1, 2, 3).double(), w.double(), b.double(), padding=3).permute(0, 2, 3, 4, 1).float()
     assert float((res[0] - ref).abs().max()) < 2e-5 * float(ref.abs().max())
 

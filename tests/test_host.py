@@ -48,6 +48,76 @@ def test_library_exports_every_declared_symbol():
     assert l.wdno_version() >= 100 and l.wdno_strerror(-1) == b'invalid argument'
 
 
+def _debug_modes():
+    """[(name, value)] of the X-macro list in csrc/debug_modes.h."""
+    text = open(os.path.join(ROOT, 'wdno_amd', 'csrc', 'debug_modes.h')).read()
+    return [(n, int(v)) for n, v in re.findall(r'^\s*X\((WDNO_DBG_\w+),\s*(\d+)\)', text, re.M)]
+
+
+def test_debug_modes_have_one_list_and_every_setter_uses_it():
+    """csrc/debug_modes.h is the only list: unique names and values; no bare number is compared with the mode anywhere in csrc/ (0 apart); every
+    number that a test or a tool passes to debug_mode( / wdno_set_debug( / WDNO_DEBUG=, or keeps in a module-level DBG_* constant, is listed."""
+    modes = _debug_modes()
+    values = [v for _, v in modes]
+    assert len(modes) >= 20 and 0 in values, modes
+    assert len(set(values)) == len(values) and len({n for n, _ in modes}) == len(modes), modes
+    csrc = os.path.join(ROOT, 'wdno_amd', 'csrc')
+    externs = []
+    for f in sorted(os.listdir(csrc)):
+        for i, line in enumerate(open(os.path.join(csrc, f)), 1):
+            m = re.search(r'(?:wdno_debug_mode|\.debug|dbg) *(?:==|!=|>=) *([0-9]+)', line)
+            assert m is None or m.group(1) == '0', f'{f}:{i}: bare debug-mode number: {line.strip()}'
+            if 'extern int wdno_debug_mode' in line:
+                externs.append(f)
+    assert externs == ['debug_modes.h'], externs
+    setter = re.compile(r'(?:debug_mode\(|wdno_set_debug\(|WDNO_DEBUG=)\s*(\d+)|^DBG_[A-Z0-9_, ]+=\s*(\d+(?:\s*,\s*\d+)*)', re.M)
+    seen = set()
+    for top in ('tests', 'tools'):
+        for d, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if f.endswith(('.py', '.sh')):
+                    for a, b in setter.findall(open(os.path.join(d, f), errors='replace').read()):
+                        for v in re.findall(r'\d+', a or b):
+                            assert int(v) in values, f'{os.path.join(d, f)} sets debug mode {v}, which csrc/debug_modes.h does not list'
+                            seen.add(int(v))
+    assert {5, 11, 45, 57, 70} <= seen, seen          # the scan really finds the call sites
+
+
+def test_set_debug_refuses_what_is_not_listed(monkeypatch):
+    """wdno_set_debug: 0 for every listed value; WDNO_EINVAL, and the mode left as it was, for a retired number and for one that never existed.
+    _lib.debug_mode() and the WDNO_DEBUG path of _lib.load() raise on those."""
+    import ctypes
+    from wdno_amd import _lib
+    lib = _lib.load()
+    current = ctypes.c_int.in_dll(lib, 'wdno_debug_mode')
+    retired, never_used = 58, 4242
+    listed = [v for _, v in _debug_modes()]
+    assert retired not in listed and never_used not in listed
+    try:
+        for v in listed:
+            assert lib.wdno_set_debug(v) == 0 and current.value == v
+        keep = listed[-1]
+        for bad in (retired, never_used, -1):
+            assert lib.wdno_set_debug(bad) == -1 and current.value == keep          # WDNO_EINVAL
+        lib.wdno_set_debug(0)
+        for bad in (retired, never_used):
+            with pytest.raises(RuntimeError, match='invalid argument'):
+                with _lib.debug_mode(bad):
+                    raise AssertionError('body ran under a refused mode')
+            assert current.value == 0
+        with _lib.debug_mode(keep):
+            assert current.value == keep
+        assert current.value == 0
+        monkeypatch.setattr(_lib, '_lib', None)
+        monkeypatch.setenv('WDNO_DEBUG', str(retired))
+        with pytest.raises(RuntimeError, match=f'WDNO_DEBUG={retired}'):
+            _lib.load()
+        monkeypatch.setenv('WDNO_DEBUG', str(keep))
+        assert _lib.load() is not None and current.value == keep
+    finally:
+        lib.wdno_set_debug(0)
+
+
 def test_state_dict_layout_matches_reference(trees):
     with torch.device('meta'):
         a = trees['Unet2D'](dim=128, dim_mults=(1, 2, 4, 8), channels=9, resnet_block_groups=1)

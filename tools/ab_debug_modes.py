@@ -1,7 +1,7 @@
 """Same-process A/B of the graph-replayed smoke training step (and, optionally, the batch-8 / batch-1 sampling step) under library debug modes:
 alternating repetitions of `--steps` steps each, one captured graph per arm (the kernel-side switch is read at launch / capture time).
-    python tools/ab_debug_modes.py 0 71 [--steps 40] [--reps 3] [--sampling]
-Round 6: 71 = GroupNorm finalize kernels as one block per sample (round 5); 70 = the round-5 item plan of the window weight gradient."""
+    python tools/ab_debug_modes.py 0 70 [--steps 40] [--reps 3] [--sampling]
+70 = the round-5 item plan of the window weight gradient; wdno_amd/csrc/debug_modes.h lists the modes, a number that is not there raises."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,7 +27,7 @@ for _ in range(3):
     ts.step(x)
 caps = {}
 for m in modes:
-    lib.wdno_set_debug(max(m, 0))
+    ops._lib.check(lib.wdno_set_debug(max(m, 0)), f'debug mode {m}')
     ops.DEFER_WGRAD_REDUCE = m != -1
     ops.DEFER_ROW_SUMS = m != -2
     ts._cap = None

@@ -1,5 +1,5 @@
-"""Temporal attention (24 frames, rotary + relative-position bias) at the three U-Net levels: old thread-per-row kernels
-(debug 5) vs the one-wave-per-item MFMA kernels."""
+"""Temporal attention (24 frames, rotary + relative-position bias) at the three U-Net levels: the generic-length
+MFMA kernels (library debug mode 44) vs the 24-token instantiation the default takes."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -4,7 +4,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from wdno_amd import ops
-lib = ops._lib_()
 CASES = [
     ('l0 3x3x3 64->64', (8, 24, 40, 40, 64), (64, 64, 3, 3, 3)),
     ('l0 3x3x3 128->64', (8, 24, 40, 40, 128), (64, 128, 3, 3, 3)),
@@ -29,8 +28,7 @@ for name, xs, ws in CASES:
     flops = 2.0 * y.numel() * c * 27
     out = []
     for mode in (int(os.environ.get('MODE_A', '6')), 0, int(os.environ.get('MODE_A', '6')), 0):
-        lib.wdno_set_debug(mode)
-        t = timeit(lambda: ops.conv_wgrad_h3(xpl, tuple(xs[:4]), ypl, tuple(xs[1:4]), (3, 3, 3), (1, 1, 1), (1, 1, 1)))
+        with ops._lib.debug_mode(mode):          # (raises on a MODE_A the library does not know)
+            t = timeit(lambda: ops.conv_wgrad_h3(xpl, tuple(xs[:4]), ypl, tuple(xs[1:4]), (3, 3, 3), (1, 1, 1), (1, 1, 1)))
         out.append(f'm{mode} {t:6.3f} ms {flops / t / 1e9:6.1f} TF/s')
-    lib.wdno_set_debug(0)
     print(f'{name:20s} ' + ' | '.join(out), flush=True)

@@ -7,7 +7,7 @@ from video_diffusion_pytorch import video_diffusion_pytorch_conv3d as V
 _p = ops._p
 lib = ops._lib_()
 torch.manual_seed(0)
-for c, b, f, h, w, dbg in ((256, 40, 24, 4, 8, 64), (256, 40, 24, 4, 8, 0), (256, 8, 24, 10, 10, 0), (256, 1, 48, 20, 20, 0), (256, 2, 48, 20, 20, 0)):
+for c, b, f, h, w, dbg in ((256, 40, 24, 4, 8, 0), (256, 8, 24, 10, 10, 0), (256, 1, 48, 20, 20, 0), (256, 2, 48, 20, 20, 0)):
     lib.wdno_set_debug(dbg)
     blk = V.Residual(V.PreNorm(c, V.SpatialLinearAttention(c, heads=4))).cuda()
     att = blk.fn.fn

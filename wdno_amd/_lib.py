@@ -3,6 +3,7 @@
 The product path has NO fallback: if the shared library is missing or a call returns an error, a RuntimeError is
 raised. Nothing in this package computes on the CPU.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -201,8 +202,12 @@ def load():
         fn.restype = res
         fn.argtypes = args
     _lib = lib
-    if os.environ.get('WDNO_DEBUG'):          # kernel-selection switches for A/B measurements (see the `debug` notes in csrc/)
-        lib.wdno_set_debug(int(os.environ['WDNO_DEBUG']))
+    if os.environ.get('WDNO_DEBUG'):          # kernel-selection switches for A/B measurements (csrc/debug_modes.h is the list)
+        try:
+            check(lib.wdno_set_debug(int(os.environ['WDNO_DEBUG'])), f"WDNO_DEBUG={os.environ['WDNO_DEBUG']}")
+        except RuntimeError:
+            _lib = None                       # a stale number raises on every load(), not only the first
+            raise
     return lib
 
 
@@ -212,3 +217,14 @@ def check(code, what):
         msg = lib.wdno_strerror(code).decode()
         hip = lib.wdno_last_hip_error().decode() if code == -2 else ''
         raise RuntimeError(f'{what} failed: {msg} ({code}) {hip}')
+
+
+@contextlib.contextmanager
+def debug_mode(mode):
+    """Run the body under library debug mode `mode` (csrc/debug_modes.h), back to 0 on exit. Raises if the library refuses the number."""
+    lib = load()
+    check(lib.wdno_set_debug(mode), f'wdno_set_debug({mode})')
+    try:
+        yield
+    finally:
+        lib.wdno_set_debug(0)

@@ -1,6 +1,7 @@
 // api.cpp -- library-level entry points of libwdno_hip (error strings, version).
 #include <hip/hip_runtime.h>
 #include "common.h"
+#include "debug_modes.h"
 
 thread_local hipError_t wdno_tls_last_hip_error = hipSuccess;
 
@@ -17,6 +18,15 @@ extern "C" const char* wdno_strerror(int code) {
 extern "C" int wdno_version(void) { return 100; }
 extern "C" const char* wdno_last_hip_error(void) { return hipGetErrorString(wdno_tls_last_hip_error); }
 
-// diagnostics hook used by tools/bench_conv.py (ablation of the convolution pipeline); 0 in production
-int wdno_debug_mode = 0;
-extern "C" int wdno_set_debug(int mode) { wdno_debug_mode = mode; return 0; }
+// kernel-selection switches for A/B measurements and tests (debug_modes.h is the list); 0 in production
+int wdno_debug_mode = WDNO_DBG_OFF;
+extern "C" int wdno_set_debug(int mode) {
+  switch (mode) {
+#define WDNO_DBG_CASE(name, value) case name:
+    WDNO_DEBUG_MODES(WDNO_DBG_CASE)
+#undef WDNO_DBG_CASE
+      wdno_debug_mode = mode;
+      return WDNO_OK;
+    default: return WDNO_EINVAL;
+  }
+}

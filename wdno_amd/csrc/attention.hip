@@ -8,7 +8,7 @@
 //    global memory (each lane supplies one k and one v element per MFMA); the per-token 32x32 mat-vecs run
 //    on the vector ALU with the context broadcast from LDS.
 #include "common.h"
-extern int wdno_debug_mode;
+#include "debug_modes.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define DH 32
@@ -1303,10 +1303,10 @@ static int attn_num_cus() {
 // Grid of the one-wave-per-item kernels: exactly the blocks that are RESIDENT together (blocks per CU x CUs), each wave walking over
 // its items with a grid stride. The first versions launched up to 4096 / 2048 blocks: several rounds of the resident set with the last
 // one partly empty (2048 blocks on 768 slots = 2.67 rounds), and waves with 3 or 4 items each (a 28 % imbalance at the 40 x 40
-// level); with 768 / 1024 blocks every wave gets 12-17 items, i.e. at most one item of imbalance. wdno_debug 41: the old caps (A/B).
-static int64_t attn_grid(int64_t items, int blocks_per_cu, int64_t old_cap) {
+// level); with 768 / 1024 blocks every wave gets 12-17 items, i.e. at most one item of imbalance.
+static int64_t attn_grid(int64_t items, int blocks_per_cu) {
   int64_t nb = (items + AM_WAVES - 1) / AM_WAVES;
-  const int64_t cap = wdno_debug_mode == 41 ? old_cap : (int64_t)blocks_per_cu * attn_num_cus();
+  const int64_t cap = (int64_t)blocks_per_cu * attn_num_cus();
   return nb > cap ? cap : nb;
 }
 static int attn_fill(AttnP& p, const wdno_attn_desc* d, float scale, int threads) {
@@ -1337,20 +1337,20 @@ extern "C" int wdno_attn_fwd_amax(const float* qkv, const float* rot_cos, const 
   int rc = attn_fill(p, d, scale, ATT_THREADS);
   if (rc) return rc;
   if (d->n_tok > 1024) return WDNO_EUNSUPPORTED;
-  if (d->n_tok <= 32 && wdno_debug_mode != 5) {                  // one 32x32 MFMA tile per (unit, head): one wave per item
-    const int64_t nb = attn_grid(p.n_items, 4, 4096);
+  if (d->n_tok <= 32 && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {                  // one 32x32 MFMA tile per (unit, head): one wave per item
+    const int64_t nb = attn_grid(p.n_items, 4);
     p.amax_rec = amax_rec;
-    (d->n_tok == 24 && wdno_debug_mode != 44 ? attn_fwd_mfma_kernel<24> : attn_fwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
+    (d->n_tok == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? attn_fwd_mfma_kernel<24> : attn_fwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
     return wdno_check_launch();
   }
-  if (d->n_tok <= 64 && wdno_debug_mode != 5) {                  // two 32-wide tiles of keys and of queries per item
+  if (d->n_tok <= 64 && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {                  // two 32-wide tiles of keys and of queries per item
     p.amax_rec = amax_rec;
     attn_fwd_mfma64_launch(qkv, rot_cos, rot_sin, bias, out, p, as_stream(s));
     return wdno_check_launch();
   }
-  if (!rot_cos && !bias && wdno_debug_mode != 5 && wdno_debug_mode != 67 && wdno_debug_mode != 69) {      // (debug 69: forward and backward thread per row)      // key tiles with an online softmax, one wave per tile of 32 queries (debug 67: thread per row)
+  if (!rot_cos && !bias && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV && wdno_debug_mode != WDNO_DBG_ATTN_FWD_ROWS) {      // key tiles with an online softmax, one wave per tile of 32 queries (WDNO_DBG_ATTN_FWD_ROWS: thread per row)
     const int ntile = (d->n_tok + 31) / 32;
-    const int64_t nb = attn_grid(p.n_items * ntile, 3, (int64_t)3 * attn_num_cus());
+    const int64_t nb = attn_grid(p.n_items * ntile, 3);
     p.amax_rec = amax_rec;
     attn_fwd_mfma_tiled_kernel<<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, p);
     return wdno_check_launch();
@@ -1365,14 +1365,14 @@ extern "C" int wdno_attn_fwd_planes(const float* qkv, const float* rot_cos, cons
   int rc = attn_fill(p, d, scale, ATT_THREADS);
   if (rc) return rc;
   if (d->n_tok > 64 || !out_hi || (out_lo && (!out_scale || !rec_qkv))) return WDNO_EUNSUPPORTED;      // out_lo == NULL: one bf16 plane
-  const int64_t nb = attn_grid(p.n_items, 4, 4096);
+  const int64_t nb = attn_grid(p.n_items, 4);
   p.amax_rec = amax_rec;
   p.pl_hi = (_Float16*)out_hi; p.pl_lo = (_Float16*)out_lo; p.rec_qkv = rec_qkv; p.pl_scale = out_scale;
   if (d->n_tok > 32) {
     attn_fwd_mfma64_launch(qkv, rot_cos, rot_sin, bias, out, p, as_stream(s));
     return wdno_check_launch();
   }
-  (d->n_tok == 24 && wdno_debug_mode != 44 ? attn_fwd_mfma_kernel<24> : attn_fwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
+  (d->n_tok == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? attn_fwd_mfma_kernel<24> : attn_fwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
   return wdno_check_launch();
 }
 static int attn_fwd_rows(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out, AttnP& p,
@@ -1388,7 +1388,7 @@ static int attn_fwd_rows(const float* qkv, const float* rot_cos, const float* ro
 // blocks of the backward launch (= number of dbias partials) and the workspace that holds them
 static int64_t attn_bwd_blocks(const wdno_attn_desc* d) {
   const int64_t items = (int64_t)d->n_uo * d->n_ui * d->heads;
-  if (d->n_tok <= 32 && wdno_debug_mode != 5) return attn_grid(items, ATT_BWD_BLOCKS_PER_CU, 2048);
+  if (d->n_tok <= 32 && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) return attn_grid(items, ATT_BWD_BLOCKS_PER_CU);
   int ipb = ATT_BWD_THREADS / d->n_tok;
   if (ipb < 1) ipb = 1;
   int64_t groups = (items + ipb - 1) / ipb;
@@ -1419,18 +1419,18 @@ extern "C" int wdno_attn_bwd_amax(const float* qkv, const float* rot_cos, const 
   const int n = d->n_tok;
   if (dbias && (!ws || ws_bytes < wdno_attn_bwd_ws_bytes(d))) return WDNO_EWORKSPACE;
   float* part = dbias ? (float*)ws : nullptr;           // the kernels write per-block partials; the reduce below writes dbias
-  // one wave per item on MFMA tiles (debug 5: thread-per-row kernel below); 116 registers and 9 KB of LDS per wave, so four
+  // one wave per item on MFMA tiles (WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV: thread-per-row kernel below); 116 registers and 9 KB of LDS per wave, so four
   // waves per SIMD hide its five dependent load phases (0.94 vs 1.17 ms at the 40 x 40 level)
-  if (n <= 32 && wdno_debug_mode != 5) {
+  if (n <= 32 && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {
     size_t lds2 = ((size_t)AM_WAVES * (2 * 32 * AM_TS + 32) + (dbias && d->heads != AM_WAVES ? (size_t)d->heads * n * n : 0)) * sizeof(float);      // (heads == AM_WAVES: the partial lives in registers)
     const int64_t nb = attn_bwd_blocks(d);                   // also the number of dbias partials
     p.amax_rec = amax_rec;
-    (d->n_tok == 24 && wdno_debug_mode != 44 ? attn_bwd_mfma_kernel<24> : attn_bwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, lds2, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p);
+    (d->n_tok == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? attn_bwd_mfma_kernel<24> : attn_bwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, lds2, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p);
     rc = wdno_check_launch();
     return (rc || !dbias) ? rc : attn_dbias_reduce(part, nb, dbias, d, s);
   }
-  // more than 64 tokens without rotation / bias (the mid spatial block): key / query tiles on the exact-fp32 matrix instruction (debug 68: thread per row)
-  if (n > 64 && n <= ATT_TILED_MAXTOK && !rot_cos && !bias && !dbias && out && wdno_debug_mode != 5 && wdno_debug_mode != 68 && wdno_debug_mode != 69) {
+  // more than 64 tokens without rotation / bias (the mid spatial block): key / query tiles on the exact-fp32 matrix instruction (WDNO_DBG_ATTN_BWD_ROWS: thread per row)
+  if (n > 64 && n <= ATT_TILED_MAXTOK && !rot_cos && !bias && !dbias && out && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV && wdno_debug_mode != WDNO_DBG_ATTN_BWD_ROWS) {
     int64_t nb = p.n_items;
     const int64_t cap = 2LL * attn_num_cus();
     if (nb > cap) nb = cap;
@@ -1451,13 +1451,13 @@ extern "C" int wdno_attn_bwd_planes(const float* qkv, const float* rot_cos, cons
   int rc = attn_fill(p, d, scale, ATT_BWD_THREADS);
   if (rc) return rc;
   const int n = d->n_tok;
-  if (n > 32 || wdno_debug_mode == 5 || !dqkv_hi || (dqkv_lo && (!dqkv_scale || !rec_qkv || !rec_dout))) return WDNO_EUNSUPPORTED;      // dqkv_lo == NULL: one bf16 plane, no scale
+  if (n > 32 || wdno_debug_mode == WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV || !dqkv_hi || (dqkv_lo && (!dqkv_scale || !rec_qkv || !rec_dout))) return WDNO_EUNSUPPORTED;      // dqkv_lo == NULL: one bf16 plane, no scale
   if (dbias && (!ws || ws_bytes < wdno_attn_bwd_ws_bytes(d))) return WDNO_EWORKSPACE;
   float* part = dbias ? (float*)ws : nullptr;
   size_t lds2 = ((size_t)AM_WAVES * (2 * 32 * AM_TS + 32) + (dbias && d->heads != AM_WAVES ? (size_t)d->heads * n * n : 0)) * sizeof(float);      // (heads == AM_WAVES: the partial lives in registers)
   const int64_t nb = attn_bwd_blocks(d);
   p.pl_hi = (_Float16*)dqkv_hi; p.pl_lo = (_Float16*)dqkv_lo; p.rec_qkv = rec_qkv; p.rec_dout = rec_dout; p.pl_scale = dqkv_scale;
-  (d->n_tok == 24 && wdno_debug_mode != 44 ? attn_bwd_mfma_kernel<24> : attn_bwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, lds2, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, nullptr, part, p);
+  (d->n_tok == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? attn_bwd_mfma_kernel<24> : attn_bwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, lds2, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, nullptr, part, p);
   rc = wdno_check_launch();
   return (rc || !dbias) ? rc : attn_dbias_reduce(part, nb, dbias, d, s);
 }
@@ -1466,8 +1466,8 @@ static int attn_bwd_rows(const float* qkv, const float* rot_cos, const float* ro
   const int n = d->n_tok;
   // 129 .. 576 tokens: nothing n x n is stored (attn_bwd_big_kernel) -- and 64 .. 128 tokens too when the kernel takes the case (no rotation, no bias):
   // the thread-per-row kernel keeps P and dS (2 n^2 floats: 81 KB at the mid block's 100 tokens) in LDS, one block per CU; 27 KB and five blocks per CU
-  // here: 305 -> 246 us for the mid spatial attention of the smoke U-Net (debug 61: the old routing)
-  if (n > ATT_BWD_THREADS || (wdno_debug_mode != 61 && n >= 64 && !rot_cos && !bias && !dbias)) {
+  // here: 305 -> 246 us for the mid spatial attention of the smoke U-Net
+  if (n > ATT_BWD_THREADS || (n >= 64 && !rot_cos && !bias && !dbias)) {
     if (n > ATT_BIG_MAXTOK || rot_cos || bias || dbias) return WDNO_EUNSUPPORTED;
     const size_t lds = ((size_t)2 * n * DH + 3 * n) * sizeof(float);
     (void)hipFuncSetAttribute((const void*)attn_bwd_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1662,7 +1662,7 @@ static int la_ctx_chunks(int64_t units, int heads, int n_tok) {
   int64_t c = (2 * (int64_t)attn_num_cus() + uh - 1) / uh;
   if (c > n_tok / 128) c = n_tok / 128;
   if (c > LA_MAXCHUNKS) c = LA_MAXCHUNKS;
-  if (c < 1 || wdno_debug_mode == 52) c = 1;                  // debug 52: one block per (unit, head) (A/B)
+  if (c < 1) c = 1;
   return (int)c;
 }
 template <int MODE>
@@ -2097,7 +2097,7 @@ extern "C" int wdno_linattn_fwd_amax(const float* qkv, float* out, float* kstats
   // (chunk partials of the context go through `out`, which only the output kernel below writes: units * heads * chunks * 1024 floats
   // <= units * n_tok * HD because chunks <= n_tok / 128)
   la_ctx_launch<0>(qkv, nullptr, kstats, nullptr, ctx, nullptr, out, units, n_tok, heads, scale, st);
-  if (wdno_debug_mode != 5) {            // debug 5: the thread-per-token kernel
+  if (wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {            // else: the thread-per-token kernel
     linattn_out_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)cdiv(n_tok, 128)), 256, 0, st>>>(qkv, ctx, out, n_tok, heads, scale, amax_rec);
     return wdno_check_launch();
   }
@@ -2120,7 +2120,7 @@ extern "C" int wdno_linattn_bwd_amax(const float* qkv, const float* dout, const 
   float* tvec = dctx + (size_t)units * heads * DH * DH;
   float* cpart = ws_bytes >= wdno_linattn_ws_bytes(units, heads) && units * heads <= 2 * (int64_t)attn_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
   la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, st);
-  if (wdno_debug_mode != 5) {            // debug 5: the thread-per-token kernel
+  if (wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {            // else: the thread-per-token kernel
     const size_t lds2 = ((size_t)(2 + 4 * 3) * LAM_TILE + 3 * DH) * sizeof(float);
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute((const void*)linattn_bwd_tok_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); attr_done = true; }

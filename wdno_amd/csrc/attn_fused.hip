@@ -23,8 +23,6 @@
 //     summed through LDS together with the residual x (kept in registers by the lanes that loaded it), one coalesced store per row.
 #include "attn_fused.h"
 
-extern int wdno_debug_mode;
-
 
 __global__ __launch_bounds__(256, 2) void tattn_fused_fwd_kernel(TFusedP p) {
   __shared__ __attribute__((aligned(16))) _Float16 Ah[32 * TF_AST];
@@ -278,7 +276,7 @@ int wdno_tattn_fused_fwd_wide_launch(const TFusedP& p, int C, hipStream_t st);
 extern "C" int wdno_tattn_fused_takes(int C, int n_tok, int heads) {
   if (heads != TF_HEADS) return 0;
   if (C == TF_C) return n_tok == TF_NT || n_tok == 48;
-  return (C == 128 || C == 256) && n_tok == TF_NT && wdno_debug_mode != 62;
+  return (C == 128 || C == 256) && n_tok == TF_NT;
 }
 
 extern "C" int wdno_tattn_fused_fwd(const float* x, const float* gamma, float eps, const void* wq_hi, const void* wq_lo, const float* wq_scale,

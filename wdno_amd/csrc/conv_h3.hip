@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void conv_fwd_h3_kernel(const _Float16* __rest
   int4v ah[2][AROWS], al[2][AROWS], bh[2][BROWS], bl[2][BROWS];     // two register sets: loads run 2 steps ahead
   auto load_tile = [&](auto SET) {
     constexpr int S = decltype(SET)::value;
-    const bool r_ok = l_r < p.R && p.debug != 1;
+    const bool r_ok = l_r < p.R;
     const int chunk_off = l_chunk * HBK;
 #pragma unroll
     for (int i = 0; i < AROWS; ++i) {
@@ -563,26 +563,26 @@ static int conv_fwd_16(const void* xh, const void* xl, const float* sx, const vo
   const int K = g->K;
   auto blocks = [&](int bm, int bn) { return cdiv64(P, bm) * cdiv(K, bn); };
   // problems with at least 100 tiles: persistent LDS-DMA kernels (256x64 / 128x128 tiles, 64x64 per compute wave); even with
-  // fewer tiles than CUs they beat the register-staged kernels (l2 512->128: 0.36 -> 0.24 ms). debug: 5 = never, 7 = always, 8 = always and not the tap-resident variant, 30 / 31 = always with the five-row tile shapes (conv_h3d.hip)
+  // fewer tiles than CUs they beat the register-staged kernels (l2 512->128: 0.36 -> 0.24 ms). WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV = never, _FORCE_DMA_CONV = always, _CHUNKED_DMA_CONV = always and not the tap-resident variant, _FORCE_TILES_160 / _320 = always with the five-row tile shapes (conv_h3d.hip)
   const int dbg = wdno_debug_mode;
-  // ... and the tap-resident kernel (stride 1, equal grids, 3-wide) has 64 x 64 / 128 x 64 tiles for problems of fewer tiles (debug 53: not)
-  const bool small_tap = p.identity_out && wdno_conv_h3t_takes(*g) && g->kw == 3 && dbg != 53 && blocks(64, 64) >= 64;
-  if (dbg != 5 && dbg != 3 && dbg != 1 && (dbg == 7 || dbg == 8 || dbg == 30 || dbg == 31 || dbg == 54 || dbg == 55 || small_tap || (K > 64 ? blocks(128, 128) : blocks(256, 64)) >= 100)) {
+  // ... and the tap-resident kernel (stride 1, equal grids, 3-wide) has 64 x 64 / 128 x 64 tiles for problems of fewer tiles
+  const bool small_tap = p.identity_out && wdno_conv_h3t_takes(*g) && g->kw == 3 && blocks(64, 64) >= 64;
+  if (dbg != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV && (dbg == WDNO_DBG_FORCE_DMA_CONV || dbg == WDNO_DBG_CHUNKED_DMA_CONV || dbg == WDNO_DBG_FORCE_TILES_160 || dbg == WDNO_DBG_FORCE_TILES_320 || small_tap || (K > 64 ? blocks(128, 128) : blocks(256, 64)) >= 100)) {
     rc = wdno_conv_fwd_h3_dma(xh, LP ? nullptr : xl, wph, LP ? nullptr : wpl, sx, sw, bias, residual, y, p, st, 3);
     if (rc == WDNO_OK) return wdno_check_launch();
     if (rc != WDNO_EUNSUPPORTED) return rc;
   }
   if (K > 64) {
-    if ((blocks(128, 128) >= 512 || blocks(64, 128) < 2 * blocks(128, 128)) && wdno_debug_mode != 3) rc = launch_h3<128, 128, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
+    if (blocks(128, 128) >= 512 || blocks(64, 128) < 2 * blocks(128, 128)) rc = launch_h3<128, 128, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
     // fewer 64 x 128 tiles than CUs (the 8 x 8 level of the Burgers U-Net at batch 16: 128 tiles of 288 steps each): 64 x 64 tiles
-    else if (blocks(64, 128) < 200 && wdno_debug_mode != 18) {
+    else if (blocks(64, 128) < 200) {
       // ... and when even those leave CUs with a single block of several hundred steps, two blocks per tile (split over the tap rows)
-      if (blocks(64, 64) <= 384 && g->kd * g->kh >= 2 && p.nsteps >= 64 && p.identity_out && residual != y && !LP && wdno_debug_mode != 19) p.ksplit = 2;
+      if (blocks(64, 64) <= 384 && g->kd * g->kh >= 2 && p.nsteps >= 64 && p.identity_out && residual != y && !LP) p.ksplit = 2;
       rc = launch_h3<64, 64, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
     }
     else rc = launch_h3<64, 128, 1, 4, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
   } else {
-    if ((blocks(128, 64) >= 512 || P <= 128) && wdno_debug_mode != 3) rc = launch_h3<128, 64, 4, 1, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
+    if (blocks(128, 64) >= 512 || P <= 128) rc = launch_h3<128, 64, 4, 1, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
     else rc = launch_h3<64, 64, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
   }
   if (rc) return rc;
@@ -910,7 +910,7 @@ __global__ __launch_bounds__(256) void wgrad_h3_reduce_kernel(const float* __res
 
 static void wgrad_h3_plan(WgradHP& w, const wdno_conv_geom* g) {
   fill_params(w.c, g);
-  w.xcd_group = wdno_debug_mode != 6;      // debug 6: plain block order (the A/B)
+  w.xcd_group = wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING;      // plain block order (the A/B)
   const int BM = g->K > 64 ? 128 : 64;
   w.tiles_k = cdiv(g->K, BM);
   // column tile of the kw*C run: 192 for the wide-K kernel (64 x 96 per wave beats 64 x 64), and for K <= 64 only when it
@@ -964,8 +964,8 @@ static int wgrad_h3_partials(const void* xh, const void* xl, const float* sx, co
     return WDNO_EUNSUPPORTED;        // 32-bit buffer offsets
   WgradHP w;
   wgrad_h3_plan(w, g);
-  // persistent LDS-DMA kernel for everything it takes (debug 5 = never); the register-staged kernels below are the fallback
-  if (wdno_debug_mode != 5) {
+  // persistent LDS-DMA kernel for everything it takes (WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV = never); the register-staged kernels below are the fallback
+  if (wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {
     int bm, bn, splits, pps, sp_mode;
     wdno_wgrad_h3d_plan(g, &bm, &bn, &splits, &pps, &sp_mode);
     size_t need_d = (size_t)splits * g->kd * g->kh * (size_t)g->K * w.c.R * sizeof(float);
@@ -1090,8 +1090,8 @@ __global__ __launch_bounds__(256) void wgrad_h3_reduce_tile_kernel(const float* 
 // which of the two reductions a layer takes, and with how many blocks (shared by the per-layer launch and the multi-tensor one)
 static bool wgrad_h3_reduce_tiled(int splits, const wdno_conv_geom* g, int Kn, int Cn) {
   const int T = g->kd * g->kh * g->kw;
-  const bool big = (int64_t)Kn * cdiv(Cn, 64) >= 512 && splits <= 8 && wdno_debug_mode != 39;
-  return T <= 64 && (splits <= 2 || big) && wdno_debug_mode != 38;             // debug 38: the scatter kernel (A/B)
+  const bool big = (int64_t)Kn * cdiv(Cn, 64) >= 512 && splits <= 8;
+  return T <= 64 && (splits <= 2 || big);
 }
 
 // ---- every pending split reduction of a backward pass in ONE launch (round 6). A training step ran 58 of these reductions, 5-10 us each, one behind

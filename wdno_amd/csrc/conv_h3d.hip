@@ -123,7 +123,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
     const int l_dx0 = l_dx, l_cc0 = l_cc;
     const int step_dx = 32 / g.C, step_cc = 32 % g.C;
     if (my_tiles > 0) setup_tile(0);
-    const bool no_dma = p.debug == 21 || p.debug >= 100;             // ablation (tools/bench_conv.py): compute waves alone, on stale LDS contents
+    const bool no_dma = p.debug == WDNO_DBG_NO_DMA || p.debug >= WDNO_DBG_NO_DMA_OFFSET;             // ablation (tools/bench_conv.py): compute waves alone, on stale LDS contents
     auto issue_step = [&](int stage) {
       const bool live = c_tile < my_tiles;
       const unsigned need_t = live ? ((1u << s_dz) | (1u << (8 + s_dy))) : 0x80000000u;      // bit 31 is never set in a mask
@@ -240,10 +240,10 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
   };
   const float inv = LP ? 1.0f : 1.0f / (sx[0] * sw[0]);
   int stage = 0;
-  // debug 23 / 24 / 26 (tools/bench_conv.py --stamps): the amax record carries this wave's shader cycles in the kernel / in
+  // WDNO_DBG_STAMP_CYCLES / _EPILOGUE / _REALTIME (tools/bench_conv.py --stamps): the amax record carries this wave's shader cycles in the kernel / in
   // the tile epilogues / its 100 MHz wall ticks instead of max|y|
-  const int sdbg = p.debug >= 100 ? p.debug - 100 : p.debug;      // 1xx = the same stamp with the DMA issue switched off (21)
-  const bool stamps = sdbg == 23 || sdbg == 24 || sdbg == 26;
+  const int sdbg = p.debug >= WDNO_DBG_NO_DMA_OFFSET ? p.debug - WDNO_DBG_NO_DMA_OFFSET : p.debug;      // the same stamp with the DMA issue switched off (WDNO_DBG_NO_DMA)
+  const bool stamps = sdbg == WDNO_DBG_STAMP_CYCLES || sdbg == WDNO_DBG_STAMP_EPILOGUE || sdbg == WDNO_DBG_STAMP_REALTIME;
   const uint64_t c_begin = stamps ? __builtin_amdgcn_s_memtime() : 0, r_begin = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
   uint64_t c_epi = 0;
   for (int t = 0; t < my_tiles; ++t) {
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
     }
     if (stamps) c_epi += __builtin_amdgcn_s_memtime() - e_begin;
   }
-  if (stamps) am = sdbg == 23 ? (float)(__builtin_amdgcn_s_memtime() - c_begin) : sdbg == 24 ? (float)c_epi : (float)(__builtin_amdgcn_s_memrealtime() - r_begin);
+  if (stamps) am = sdbg == WDNO_DBG_STAMP_CYCLES ? (float)(__builtin_amdgcn_s_memtime() - c_begin) : sdbg == WDNO_DBG_STAMP_EPILOGUE ? (float)c_epi : (float)(__builtin_amdgcn_s_memrealtime() - r_begin);
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * (WM * WN) + wave);
 }
 
@@ -388,39 +388,34 @@ static int fwd_h3_dma(const void* xh, const void* xl, const void* wh, const void
   // Tile shape: the one with the least (rounds of the persistent grid) x (tile area), lightly weighted by how much operand
   // traffic a shape needs per MFMA. Examples on 256 CUs: a 256-channel layer at the 10 x 10 level is 300 tiles of 128 x 128 --
   // two rounds, the second with 44 tiles -- but 200 tiles of 192 x 128 (0.258 -> 0.196 ms); a 64-channel layer at the 20 x 20
-  // level is 300 tiles of 256 x 64 but 400 shorter ones of 192 x 64 (0.329 -> 0.267 ms). debug 9: the two original shapes only.
+  // level is 300 tiles of 256 x 64 but 400 shorter ones of 192 x 64 (0.329 -> 0.267 ms).
   const int cus = num_cus() & ~7;
   auto cost = [&](int bm, int bn, double weight) {
     return (double)(cdiv64(cdiv64(p.P, bm) * cdiv(g.K, bn), cus) * bm * bn) * weight;
   };
-  const bool narrow_only = g.K <= 64, all = wdno_debug_mode != 9;
+  const bool narrow_only = g.K <= 64;
   int best = narrow_only ? 2 : 0;
   double c = narrow_only ? cost(256, 64, 1.04) : cost(128, 128, 1.0);
-  if (!narrow_only && all && cost(192, 128, 1.0) < c) { best = 1; c = cost(192, 128, 1.0); }
-  if (!narrow_only && all && cost(256, 64, 1.04) < c) { best = 2; c = cost(256, 64, 1.04); }
-  if (all && cost(192, 64, 1.08) < c) { best = 3; c = cost(192, 64, 1.08); }
+  if (!narrow_only && cost(192, 128, 1.0) < c) { best = 1; c = cost(192, 128, 1.0); }
+  if (!narrow_only && cost(256, 64, 1.04) < c) { best = 2; c = cost(256, 64, 1.04); }
+  if (cost(192, 64, 1.08) < c) { best = 3; c = cost(192, 64, 1.08); }
   if (p.identity_out && wdno_conv_h3t_takes(g)) {
     // tap-resident kernel only: two more shapes of 20480 outputs, five MFMA row tiles per wave. On 256 CUs the 20 x 20-level layers with 128
     // output channels are 600 tiles of 128 x 128 (three rounds, the last with 88 tiles) but 480 of 160 x 128 (two rounds, 94 % full), the
     // 10 x 10-level ones with 256 are 200 of 192 x 128 (78 % of one round) but 240 of 160 x 128; 320 x 64 does the same for 64 output
-    // channels at the 20 x 20 level (240 tiles instead of 400 of 192 x 64). debug 29: without them.
-    if (all && wdno_debug_mode != 29 && g.kw == 3) {
+    // channels at the 20 x 20 level (240 tiles instead of 400 of 192 x 64).
+    if (g.kw == 3) {
       if (!narrow_only && cost(160, 128, 1.02) < c) { best = 4; c = cost(160, 128, 1.02); }
       if (cost(320, 64, 1.05) < c) { best = 5; c = cost(320, 64, 1.05); }
       // few pixels x many channels (the 16 x 16 and 8 x 8 levels of the Burgers U-Net at batch 16: 176 tiles of 192 x 64, 64 of 128 x 128):
-      // 128 x 64 and 64 x 64 tiles fill the chip; their operand traffic per MFMA is higher (weights 1.15 / 1.35). debug 53: without them.
-      if (wdno_debug_mode != 53) {
-        if (cost(128, 64, 1.15) < c) { best = 7; c = cost(128, 64, 1.15); }
-        if (cost(64, 64, 1.35) < c) { best = 6; c = cost(64, 64, 1.35); }
-      }
-      if (wdno_debug_mode == 54) best = 6;
-      if (wdno_debug_mode == 55) best = 7;
-      if (wdno_debug_mode == 30) best = narrow_only ? 5 : 4;     // tests: the new shapes on small cases
-      if (wdno_debug_mode == 31) best = 5;
-      if (wdno_debug_mode == 45 && best == 2 && (g.C % 16) == 0) best = 8;      // experiment: 128 x 64 accumulator tile per wave (conv_h3t.hip)
+      // 128 x 64 and 64 x 64 tiles fill the chip; their operand traffic per MFMA is higher (weights 1.15 / 1.35).
+      if (cost(128, 64, 1.15) < c) { best = 7; c = cost(128, 64, 1.15); }
+      if (cost(64, 64, 1.35) < c) { best = 6; c = cost(64, 64, 1.35); }
+      if (wdno_debug_mode == WDNO_DBG_FORCE_TILES_160) best = narrow_only ? 5 : 4;     // tests: the new shapes on small cases
+      if (wdno_debug_mode == WDNO_DBG_FORCE_TILES_320) best = 5;
       // ... but where those small tiles were chosen for a LONG reduction (8 x 8 x 16 samples x 1024 channels: 256 tiles of 64 x 64 with 96 stages
       // each, every stage a 33 KB delivery for 18 matrix instructions per wave -- delivery-bound, 89 vs 46 us with the DMA issue off), 128 x 128
-      // tiles whose reduction is cut into four runs fill the chip too, with 66 KB per 72 matrix instructions: 89 -> 61 us (debug 56: not).
+      // tiles whose reduction is cut into four runs fill the chip too, with 66 KB per 72 matrix instructions: 89 -> 61 us (WDNO_DBG_CONV_NO_RUN_SPLIT: not).
       // (Not where 128 x 64 tiles were chosen -- 16 x 16 x 16 samples x 512 channels: 61 us unsplit, 63 us as two runs.) Needs the caller's
       // workspace for the partial sums (wdno_conv_fwd_split_ws_bytes).
       const int split = wdno_conv_h3t_split(g, p.P, cus);

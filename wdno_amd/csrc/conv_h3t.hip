@@ -139,7 +139,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
   // compute waves derive the same per-tile stage count from t_tap_live; WHICH stages run only the producers need to know.
   constexpr bool SKIP = KW == 7 && !SP;
   const int nzb = SKIP ? p.zb_blocks : 0;
-  const bool skipping = SKIP && p.zb_blocks >= 0 && p.debug != 57;          // debug 57: every stage (A/B, bit-identity test)
+  const bool skipping = SKIP && p.zb_blocks >= 0 && p.debug != WDNO_DBG_STEM_EVERY_STAGE;          // every stage (A/B, bit-identity test)
   auto tile_live = [&](int t) {
     const int vt = xcd_swizzle((int)blockIdx.x + t * (int)gridDim.x, nvt);
     const int m0 = (vt / p.tiles_n) * BM;
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
     };
     bool fresh = true;                                             // SKIP: the cursor's tile has not issued a stage yet
     if (my_tiles > 0) setup_tile(0);
-    const bool no_dma = p.debug == 21 || p.debug >= 100;                             // ablation (tools/bench_conv.py): compute waves alone
+    const bool no_dma = p.debug == WDNO_DBG_NO_DMA || p.debug >= WDNO_DBG_NO_DMA_OFFSET;                             // ablation (tools/bench_conv.py): compute waves alone
     auto issue_stage = [&](int buf) {
       if (skipping) {
         if (fresh) {                                               // cursor on the first stage of the tile that runs
@@ -337,8 +337,8 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
       for (int b = 0; b < TN; ++b) acc[a][b] = t_mfma<LP>(fbh[set][b], fah[set][a], acc[a][b]);
   };
   const float inv = LP ? 1.0f : 1.0f / (sx[0] * sw[0]);
-  const int sdbg = p.debug >= 100 ? p.debug - 100 : p.debug;
-  const bool stamps = sdbg == 23 || sdbg == 24 || sdbg == 26;     // see conv_h3d.hip
+  const int sdbg = p.debug >= WDNO_DBG_NO_DMA_OFFSET ? p.debug - WDNO_DBG_NO_DMA_OFFSET : p.debug;
+  const bool stamps = sdbg == WDNO_DBG_STAMP_CYCLES || sdbg == WDNO_DBG_STAMP_EPILOGUE || sdbg == WDNO_DBG_STAMP_REALTIME;     // see conv_h3d.hip
   const uint64_t c_begin = stamps ? __builtin_amdgcn_s_memtime() : 0, r_begin = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
   uint64_t c_epi = 0;
   int boff = 0;                                                   // byte offset of the stage being read
@@ -358,8 +358,8 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
       const int ow = ((int)m0 + row0 + a * 32) % g.OW;                  // P < 2^31 (launch_h3t)
 #pragma unroll
       for (int dx = 0; dx < KW; ++dx) {
-        const int row = row0 + a * 32 + (p.debug == 15 ? 0 : dx);      // debug 15 / 16: bank-conflict probes (wrong results)
-        const bool ok = p.debug == 16 || (unsigned)(ow - g.pw + dx) < (unsigned)g.W;
+        const int row = row0 + a * 32 + dx;
+        const bool ok = (unsigned)(ow - g.pw + dx) < (unsigned)g.W;
         // the stand-in zero row keeps the bank slot of the real one (same row % 4, same swizzled chunk): a conflict-free 16-lane group
         // uses all 16 slots once, so a lane redirected anywhere else collides with a neighbour (measured: 13 % more LDS cycles)
         const int zrow = S::ZB + (row & (S::ZR - 1));
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
       // 2.7e-7 for the exact-fp32 kernel with its two-level sums, and that offset rode through the whole network). Two-level sums here too: the
       // accumulators of one tap row (dz, dy) -- at most ncb stages, 63 accumulations -- are added into a second set when the row is done.
       // The rows are counted from the same liveness masks as the producers' cursor, so a skipped all-zero stage changes nothing: the
-      // skipping and the non-skipping launch (debug 57) agree bit for bit.
+      // skipping and the non-skipping launch (WDNO_DBG_STEM_EVERY_STAGE) agree bit for bit.
       const unsigned allz = (1u << g.kd) - 1u, ally = (1u << g.kh) - 1u;
       const TapLive lvc = skipping ? tile_live(t) : TapLive{{allz, allz}, {ally, ally}};
       const int nst = t_live_stages(lvc, ncb, nzb);                // (not skipping: kd kh ncb made even = nstages)
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
     }
     if (stamps) c_epi += __builtin_amdgcn_s_memtime() - e_begin;
   }
-  if (stamps) am = sdbg == 23 ? (float)(__builtin_amdgcn_s_memtime() - c_begin) : sdbg == 24 ? (float)c_epi : (float)(__builtin_amdgcn_s_memrealtime() - r_begin);
+  if (stamps) am = sdbg == WDNO_DBG_STAMP_CYCLES ? (float)(__builtin_amdgcn_s_memtime() - c_begin) : sdbg == WDNO_DBG_STAMP_EPILOGUE ? (float)c_epi : (float)(__builtin_amdgcn_s_memrealtime() - r_begin);
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * (WM * WN) + wave);
 }
 
@@ -603,17 +603,17 @@ static int launch_h3t(const void* xh, const void* xl, const void* wh, const void
 // 2 = 256 x 64, 3 = 192 x 64, 4 = 160 x 128 (one wave row, four wave columns), 5 = 320 x 64).
 // ... or kw == 7 on whole 16-channel blocks with at most 64 output channels (the stem of the smoke U-Net: 42 -> 48 channels in the planes):
 // there the weight rows of a 32-channel block (7 x 64 x 64 B per plane) would not leave room for two stages, so a stage is a 16-channel
-// block with LDS rows of 32 B and one 16-deep sub-step per dx (debug 20: the chunked kernel instead).
-static bool t_stem(const wdno_conv_geom& g) { return g.kw == 7 && (g.C % 16) == 0 && g.K <= 64 && wdno_debug_mode != 20; }
+// block with LDS rows of 32 B and one 16-deep sub-step per dx.
+static bool t_stem(const wdno_conv_geom& g) { return g.kw == 7 && (g.C % 16) == 0 && g.K <= 64; }
 bool wdno_conv_h3t_takes(const wdno_conv_geom& g) {
   return g.sd == 1 && g.sh == 1 && g.sw == 1 && g.OD == g.D && g.OH == g.H && g.OW == g.W && ((g.kw == 3 && (g.C % 32) == 0) || t_stem(g)) &&
-         g.kd <= 8 && g.kh <= 8 && wdno_debug_mode != 8;
+         g.kd <= 8 && g.kh <= 8 && wdno_debug_mode != WDNO_DBG_CHUNKED_DMA_CONV;
 }
 // Runs the reduction of a 128 x 128-tiled layer is cut into (conv_h3d.hip; 1 = no split): four where that still is one round of the persistent
 // grid, of whole stages, at least 8 per run. (Two runs were measured too: 256 -> 256 channels at 16 x 16 x 16 samples 26 -> 32 us, the
 // 1024 -> 1536 data gradient at 8 x 8 116 -> 118 us -- no gain; four: 1024 -> 1024 93 -> 64, 512 -> 512 40 -> 32, 1536 -> 1024 132 -> 84 us.)
 int wdno_conv_h3t_split(const wdno_conv_geom& g, int64_t P, int cus) {
-  if (wdno_debug_mode == 56 || g.kw != 3 || (g.C % 32) || g.K < 128 || (g.K & 3)) return 1;
+  if (wdno_debug_mode == WDNO_DBG_CONV_NO_RUN_SPLIT || g.kw != 3 || (g.C % 32) || g.K < 128 || (g.K & 3)) return 1;
   const int64_t t128 = cdiv64(P, 128) * cdiv(g.K, 128);
   const int nst = g.kd * g.kh * (g.C / 32);
   return t128 * 4 <= cus && nst % 4 == 0 && nst / 4 >= 8 ? 4 : 1;
@@ -629,27 +629,24 @@ static int fwd_h3t(int shape, const void* xh, const void* xl, const void* wh, co
   if (shape == 5) return launch_h3t<320, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
   if (shape == 6) return launch_h3t<64, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);      // few pixels x many channels (Burgers 8 x 8 level)
   if (shape == 7) return launch_h3t<128, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  // experiment (debug 45, tools/bench_conv.py): 128 x 64 accumulator tile per compute wave -- 512 x 64 block tiles on 16-channel stages (rows
-  // of 32 B: two stages of 32-channel blocks would need 180 KB), 12 fragment reads per 24 matrix instructions instead of 8 per 12
-  if (shape == 8) return launch_h3t<512, 64, 4, 1, 3, 16, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
   return launch_h3t<256, 64, 4, 1, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
 }
 int wdno_conv_fwd_h3_tap(int shape, const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
                          const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
   // single-plane (bf16) mode has a third of the MFMA work per operand byte: with >= 128 output channels and enough tiles, 256 x 128
-  // tiles (64 x 128 per wave: 6 fragment reads per 8 MFMAs, 41 KB per stage) -- debug 17: the shapes of the split mode
+  // tiles (64 x 128 per wave: 6 fragment reads per 8 MFMAs, 41 KB per stage)
   if (p.g.kw == 7) {
     const int ncb = (p.g.C + 15) / 16;
     if (p.zb_blocks >= ncb) p.zb_blocks = ncb - 1;          // (a tile must keep at least its centre stage: t_live_stages)
     // less than one round of 256-pixel tiles (the stem at batch 1: 150 tiles on 256 CUs): 192-pixel tiles fill the chip and end a quarter
-    // earlier (128-pixel tiles would need a second round) -- debug 72: the 256-pixel tiles always
+    // earlier (128-pixel tiles would need a second round) -- WDNO_DBG_STEM_TILES_256: the 256-pixel tiles always
     const int cus = t_num_cus();
-    if (xl != nullptr && cdiv64(p.P, 256) < cus && cdiv64(p.P, 192) <= cus && cdiv64(p.P, 192) > cdiv64(p.P, 256) && wdno_debug_mode != 72)
+    if (xl != nullptr && cdiv64(p.P, 256) < cus && cdiv64(p.P, 192) <= cus && cdiv64(p.P, 192) > cdiv64(p.P, 256) && wdno_debug_mode != WDNO_DBG_STEM_TILES_256)
       return launch_h3t<192, 64, 2, 2, 7, 16, false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
     if (xl == nullptr) return launch_h3t<256, 64, 4, 1, 7, 16, true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
     return launch_h3t<256, 64, 4, 1, 7, 16, false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
   }
-  if (xl == nullptr && p.g.K > 64 && cdiv64(p.P, 256) * cdiv(p.g.K, 128) >= 2 * t_num_cus() && wdno_debug_mode != 17)
+  if (xl == nullptr && p.g.K > 64 && cdiv64(p.P, 256) * cdiv(p.g.K, 128) >= 2 * t_num_cus())
     return launch_h3t<256, 128, 4, 1, 3, 32, true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
   if (xl == nullptr) return fwd_h3t<true>(shape, xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
   return fwd_h3t<false>(shape, xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3d_kernel(const _Float16* __r
     };
     // ablations (tools/bench_conv.py; records are still fetched): 21 = every piece out of range (the instructions issue, nothing
     // travels), 22 = no piece instructions at all
-    const bool no_dma = p.debug == 21 || p.debug == 22, no_piece = p.debug == 22;
+    const bool no_dma = p.debug == WDNO_DBG_NO_DMA || p.debug == WDNO_DBG_WGRAD_NO_DMA_NO_PIECE, no_piece = p.debug == WDNO_DBG_WGRAD_NO_DMA_NO_PIECE;
     auto issue = [&](auto SLOT, int stage) {
       constexpr int S = decltype(SLOT)::value;
       const bool live = pc.t < my_items && !no_dma;
@@ -856,7 +856,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3s_kernel(const _Float16* __r
       dp = pbeg + dpix;
       d_off = (dp * g.K + du * 32 + dc * 8) * 2;
     };
-    const bool no_dma = p.debug == 21;                    // ablation (tools/bench_conv.py): every piece out of range
+    const bool no_dma = p.debug == WDNO_DBG_NO_DMA;                    // ablation (tools/bench_conv.py): every piece out of range
     auto issue_next = [&](int buf) {
       const unsigned sb = lds0 + buf * STAGE + pq * 1024;
       const bool xv = x_slot && q >= 0 && q < (int)p.P && (unsigned)(qd + vdz) < (unsigned)g.D && (unsigned)(qh + vdy) < (unsigned)g.H;
@@ -1043,16 +1043,16 @@ static int wd_num_cus() {
   return n;
 }
 
-// geometries of the window kernel: stride 1, equal grids, kw == 3, whole 64-channel tiles (debug 8: never; debug 11: only for
+// geometries of the window kernel: stride 1, equal grids, kw == 3, whole 64-channel tiles (WDNO_DBG_CHUNKED_DMA_CONV: never; WDNO_DBG_PER_AXIS_DWT_AND_WGRAD_WINDOW_K64: only for
 // K <= 64 -- with more output channels the windows are fetched once per 64-wide k tile)
 static bool wd_window_takes(const wdno_conv_geom* g) {
-  if (wdno_debug_mode == 8 || (wdno_debug_mode == 11 && g->K > 64)) return false;
+  if (wdno_debug_mode == WDNO_DBG_CHUNKED_DMA_CONV || (wdno_debug_mode == WDNO_DBG_PER_AXIS_DWT_AND_WGRAD_WINDOW_K64 && g->K > 64)) return false;
   return g->sd == 1 && g->sh == 1 && g->sw == 1 && g->OD == g->D && g->OH == g->H && g->OW == g->W && g->kw == 3 && g->pw == 1 &&
          (g->C % 64) == 0 && (g->K % 8) == 0;
 }
-// geometries of the seven-wide window kernel (debug 8 / 28: the chunked kernel instead)
+// geometries of the seven-wide window kernel (WDNO_DBG_CHUNKED_DMA_CONV: the chunked kernel instead)
 static bool wd_stem_takes(const wdno_conv_geom* g) {
-  if (wdno_debug_mode == 8 || wdno_debug_mode == 28) return false;
+  if (wdno_debug_mode == WDNO_DBG_CHUNKED_DMA_CONV) return false;
   return g->sd == 1 && g->sh == 1 && g->sw == 1 && g->OD == g->D && g->OH == g->H && g->OW == g->W && g->kw == 7 && g->pw == 3 &&
          g->C == 48 && (g->K % 8) == 0 && g->K <= 64 && g->kd <= 8 && g->kh <= 8;
 }
@@ -1086,8 +1086,8 @@ void wdno_wgrad_h3d_plan(const wdno_conv_geom* g, int* bm, int* bn, int* splits,
     if (splitpair) *splitpair = 0;
     // Split-pair mode (conv_wgrad_h3w_kernel): with an odd number of tap rows the last one is paired across two pixel splits instead of with an
     // empty window: tkc * (ntap / 2) * S + tkc * ceil(S / 2) items of equal length for S splits. Taken when one round of the CUs still holds
-    // them (a block then sees items of one kind only) and the items get SHORTER than in the plan above (debug 70: never -- the A/B).
-    if (splitpair && (ntap & 1) && wdno_debug_mode != 70) {
+    // them (a block then sees items of one kind only) and the items get SHORTER than in the plan above (WDNO_DBG_WGRAD_NO_SPLIT_PAIR: never -- the A/B).
+    if (splitpair && (ntap & 1) && wdno_debug_mode != WDNO_DBG_WGRAD_NO_SPLIT_PAIR) {
       const int blocks = wd_num_cus() >= 256 ? 256 : (wd_num_cus() & ~7);      // what launch_ww starts at most (it walks items <= blocks one per block)
       int64_t S = max_splits < 256 ? max_splits : 256;
       while (S >= 2 && (int64_t)tkc * (ntap / 2) * S + (int64_t)tkc * ((S + 1) / 2) > blocks) --S;
@@ -1127,7 +1127,7 @@ static void launch_wd(const void* xh, const void* xl, const void* dyh, const voi
   if (w.items < grid) grid = w.items;
   WgradDP wl = w;
   wl.xcd_chunk = 0;
-  if (grid >= 64 && wdno_debug_mode != 6) {          // debug 6: round-robin items (the A/B for the XCD grouping)
+  if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {          // WDNO_DBG_WGRAD_NO_XCD_GROUPING: round-robin items (the A/B for the XCD grouping)
     wl.xcd_chunk = cdiv(w.items, 8);
     grid = wd_num_cus() & ~7;
     if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;      // every XCD's blocks walk its chunk in whole rounds; spare blocks idle
@@ -1151,7 +1151,7 @@ static void launch_ww(const void* xh, const void* xl, const void* dyh, const voi
   if (w.items < grid) grid = w.items;
   WgradDP wl = w;
   wl.xcd_chunk = 0;
-  if (grid >= 64 && wdno_debug_mode != 6) {
+  if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {
     wl.xcd_chunk = cdiv(w.items, 8);
     grid = wd_num_cus() & ~7;
     if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;
@@ -1171,7 +1171,7 @@ static void launch_ws(const void* xh, const void* xl, const void* dyh, const voi
   if (w.items < grid) grid = w.items;
   WgradDP wl = w;
   wl.xcd_chunk = 0;
-  if (grid >= 64 && wdno_debug_mode != 6) {
+  if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {
     wl.xcd_chunk = cdiv(w.items, 8);
     grid = wd_num_cus() & ~7;
     if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;

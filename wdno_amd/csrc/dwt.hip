@@ -11,6 +11,7 @@
 // folded into the store/load addressing of the pass that touches the coefficient tensor, so no separate
 // packing kernel exists. Taps travel as kernel arguments (<= 16 per filter).
 #include "common.h"
+#include "debug_modes.h"
 #include <type_traits>
 #include <algorithm>
 #include <cstdlib>
@@ -141,7 +142,6 @@ __global__ __launch_bounds__(256) void synthesis_kernel(const float* __restrict_
 // per-axis kernels above, hence the results are BIT-IDENTICAL to them (tests compare with torch.equal).
 // Halo rows/frames of neighbouring tiles are re-read through L2: logical tile ids are laid out so that one XCD (= one L2) owns a
 // contiguous range of tiles, i.e. whole images.
-extern int wdno_debug_mode;      // 11: force the per-axis passes (A/B and bit-equality tests)
 
 // n / d for 0 <= n, n * d < 2^32 as one multiply-high (m = floor(2^32 / d) + 1): the item loops below decode (row, column)
 // from a linear index several times per item, and a hardware integer division is ~30 VALU instructions on gfx950 -- with them
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256) void dwt_synthesis_fused_kernel(const float* _
   constexpr int WB = (ND == 2) ? 3 : 2;
   constexpr int HL = L / 2;
   const int n_w = NP * 2 * EH * QW;
-  if (g.debug != 12)
+  if (g.debug != WDNO_DBG_DWT_SKIP_W_PASS)
   for (int it0 = threadIdx.x; it0 < n_w; it0 += 256 * WB) {
     float cl[WB][HL], ch[WB][HL];
     unsigned okm[WB];
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(256) void dwt_synthesis_fused_kernel(const float* _
   const int wshift = off & 1;                                // position pw <-> n_w = pw - (off & 1)
   if (ND == 3) {
     float* S2 = lds + NP * 2 * EH * NW;                      // [2 ET][2 NQH][NW]
-    if (g.debug != 13)
+    if (g.debug != WDNO_DBG_DWT_SKIP_H_PASS)
 #pragma unroll 2
     for (int it = threadIdx.x; it < NP * 2 * NQH * NW; it += 256) {
       int q = fd_div(it, g.dFW);
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(256) void dwt_synthesis_fused_kernel(const float* _
     }
     __syncthreads();
     const int64_t fs = (int64_t)g.H * g.W;
-    if (g.debug != 14)
+    if (g.debug != WDNO_DBG_DWT_SKIP_T_PASS)
     for (int it = threadIdx.x; it < 2 * nqh * NW; it += 256) {
       const int ph = fd_div(it, g.dFW), pw = it - ph * NW;
       const int nw = pw - wshift;
@@ -716,7 +716,7 @@ __global__ __launch_bounds__(256) void dwt_synthesis2_kernel(const float* __rest
 // frame is in LDS at a time (W pass -> S1, H pass -> S2, 20 KB for 8 q-rows); the T pass is an accumulation in registers: a thread owns
 // ITEMS output columns (ph, pw) and 2 NQ time samples of each, and every staged frame adds its lo / hi contribution to the <= L/2 q-frames it
 // belongs to. Frames are walked in DESCENDING order so that each accumulator receives its terms in the order i = 0, 1, .. of the
-// per-axis kernel (K = q - i): results stay BIT-IDENTICAL to it (tests/test_gpu_dwt_fused.py). wdno_debug 45: the kernel above (A/B).
+// per-axis kernel (K = q - i): results stay BIT-IDENTICAL to it (tests/test_gpu_dwt_fused.py). WDNO_DBG_DWT3_SYNTH_LDS: the kernel above (A/B).
 // The kernel is bound by VALU issue, not by memory (4 blocks per CU run concurrently; ~2.5 K wave instructions per wave at 4 cycles each were 19 of
 // its 25 us): so (a) everything that does not depend on the frame -- the (band, row, column) decode of a thread's W- and H-pass items, the
 // boundary maps, the LDS offsets -- is computed once before the frame loop, (b) an H-pass item produces BOTH rows 2 ql, 2 ql + 1 from one set
@@ -976,7 +976,7 @@ static bool fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d
   if (g.cs_img >= (1ll << 31) || (int64_t)g.T * g.H * g.W >= (1ll << 31)) return false;      // 32-bit offsets within an image
   constexpr int NQ = (ND == 3) ? 4 : 4;
   size_t lds;
-  if (ND == 3 && wdno_debug_mode != 45) {
+  if (ND == 3 && wdno_debug_mode != WDNO_DBG_DWT3_SYNTH_LDS) {
     // streaming kernel: q-rows per tile from the register budget (ITEMS columns of 2 NQ samples per thread) and a 32 KB LDS budget
     auto stream = [&](auto ITEMS_C, auto NQ_C) -> bool {
       constexpr int ITEMS = decltype(ITEMS_C)::value, NQS = decltype(NQ_C)::value;
@@ -1032,7 +1032,7 @@ static bool fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d
   g.dFW = make_fastdiv(g.FW); g.dQW = make_fastdiv(g.FW / 2); g.dEH = make_fastdiv(g.NH + E); g.dNQH2 = make_fastdiv(2 * g.NH);
   g.dQW4 = make_fastdiv((g.FW / 2 + 3) / 4); g.dRW = make_fastdiv(4 * ((g.FW / 2 + 3) / 4) + L / 2 - 1);
   g.debug = wdno_debug_mode;
-  if (ND == 2 && wdno_debug_mode != 50) {                     // debug 50: the one-tile-per-block kernel (A/B)
+  if (ND == 2) {
     const int RW = 4 * ((g.FW / 2 + 3) / 4) + L / 2 - 1;
     if (g.NH + E <= 2 * NQ + E && RW <= 256) {
       const int grid = (int)nb;
@@ -1068,7 +1068,7 @@ static bool fused_dispatch(bool analysis_dir, const float* src, float* dst, cons
 // odd-length synthesis-shaped adjoint), the caller falls back to the per-axis passes.
 static bool fused_try(bool analysis_dir, const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st,
                       const PackedStore* pk = nullptr) {
-  if ((wdno_debug_mode == 11 && !pk) || d->nd < 2) return false;
+  if ((wdno_debug_mode == WDNO_DBG_PER_AXIS_DWT_AND_WGRAD_WINDOW_K64 && !pk) || d->nd < 2) return false;
   if (!analysis_dir && d->mode == 0 && odd_rule)
     for (int a = 3 - d->nd; a < 3; ++a)
       if (d->in_dims[a] & 1) return false;

@@ -313,9 +313,8 @@ static int lf_chunks(int64_t units, int n_tok) {
 // 128 / 256 channels: linattn_fused_wide.hip (forward only; operands of pack modes 10 / 11)
 int wdno_lattn_wide_ctx_launch(const LFusedP& p, int C, unsigned grid, hipStream_t st);
 int wdno_lattn_wide_out_launch(const LFusedP& p, int C, unsigned grid, hipStream_t st);
-extern int wdno_debug_mode;
 extern "C" int wdno_lattn_fused_takes(int C, int heads, int n_tok) {
-  return (C == TF_C || ((C == 128 || C == 256) && wdno_debug_mode != 62)) && heads == TF_HEADS && n_tok >= 32;
+  return (C == TF_C || C == 128 || C == 256) && heads == TF_HEADS && n_tok >= 32;
 }
 extern "C" size_t wdno_lattn_fused_ws_bytes(int64_t units, int n_tok) {
   return ((size_t)units * lf_chunks(units, n_tok) * TF_HEADS * LF_PART + (size_t)units * TF_HEADS * 1024) * sizeof(float);

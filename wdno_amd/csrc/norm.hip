@@ -8,7 +8,6 @@
 // gradients and the two group means, then one elementwise pass for dx.
 #include "common.h"
 #include <type_traits>
-extern int wdno_debug_mode;      // 58 / 59: GroupNorm timing experiments -- the forward statistics pass / the backward reduction pass is launched TWICE (same results): the step-time difference is what the pass costs inside the step
 
 #define GN_MAXC 1024
 
@@ -597,7 +596,7 @@ static inline float* gn_cb(float* stats, int64_t N, int G) { return stats + (siz
 static inline float* gn_gb(float* stats, int64_t N, int C, int G) { return stats + (size_t)N * G * 2 + (size_t)N * C * 4; }
 // slices of groups per sample for the finalize kernels: every group its own block while the groups are narrow (the statistics of wide groups --
 // GroupNorm(1, C) of the Burgers U-Net -- are reduced by a whole block)
-static inline unsigned gn_slices(int C, int G) { return (C / G > 64 || wdno_debug_mode == 71) ? 1u : (unsigned)(G < 32 ? G : 32); }      // debug 71: one block per sample (round 5, the A/B)
+static inline unsigned gn_slices(int C, int G) { return C / G > 64 ? 1u : (unsigned)(G < 32 ? G : 32); }
 static int gn_check(int64_t N, int64_t S, int C, int G) {
   if (N <= 0 || S <= 0 || C <= 0 || G <= 0 || N > 65535) return WDNO_EINVAL;
   if ((C & 3) || C > GN_MAXC || (C % G) != 0) return WDNO_EUNSUPPORTED;
@@ -618,8 +617,7 @@ extern "C" int wdno_groupnorm_act_fwd_amax_t(const void* x, int x_bf16, const fl
   const int txp = pow2ceil(C / 4);
   const int64_t rpc = cdiv64(S, nchunk);
   hipStream_t st = as_stream(s);
-  for (int rep_ = 0; rep_ < (wdno_debug_mode == 58 ? 2 : 1); ++rep_)
-    GN_PARTIAL0(x_bf16, dim3(nchunk, (unsigned)N), 256, 0, st>>>(x, nullptr, nullptr, nullptr, part, S, C, C / G, G, txp, rpc, 0));
+  GN_PARTIAL0(x_bf16, dim3(nchunk, (unsigned)N), 256, 0, st>>>(x, nullptr, nullptr, nullptr, part, S, C, C / G, G, txp, rpc, 0));
   gn_finalize_kernel<<<dim3((unsigned)N, gn_slices(C, G)), 256, 0, st>>>(part, nullptr, gamma, beta, ss, stats, cb, gb, S, C, G, nchunk, eps);
   int gx = stream_grid(S * (C / 4), 256);
   if (gx > 512) gx = 512;
@@ -650,7 +648,7 @@ extern "C" int wdno_groupnorm_act_bwd_amax(const float* x, const float* dy, cons
   const int txp = pow2ceil(C / 4);
   const int64_t rpc = cdiv64(S, nchunk);
   hipStream_t st = as_stream(s);
-  for (int rep_ = 0; rep_ < (wdno_debug_mode == 59 ? 2 : 1); ++rep_) gn_partial_kernel<1><<<dim3(nchunk, (unsigned)N), 256, 0, st>>>(x, dy, cb, gb, part, S, C, C / G, G, txp, rpc, silu);
+  gn_partial_kernel<1><<<dim3(nchunk, (unsigned)N), 256, 0, st>>>(x, dy, cb, gb, part, S, C, C / G, G, txp, rpc, silu);
   gn_bwd_finalize_kernel<<<dim3((unsigned)N, gn_slices(C, G)), 256, 0, st>>>(part, gamma, beta, ss, gb, dgb_partial, dss, S, C, G, nchunk);
   int gx = stream_grid(S * (C / 4), 256);
   if (gx > 512) gx = 512;
@@ -683,8 +681,7 @@ extern "C" int wdno_groupnorm_act_fwd_planes_t(const void* x, int x_bf16, const 
   const int txp = pow2ceil(C / 4);
   const int64_t rpc = cdiv64(S, nchunk);
   hipStream_t st = as_stream(s);
-  for (int rep_ = 0; rep_ < (wdno_debug_mode == 58 ? 2 : 1); ++rep_)
-    GN_PARTIAL0(x_bf16, dim3(nchunk, (unsigned)N), 256, 0, st>>>(x, nullptr, nullptr, nullptr, part, S, C, C / G, G, txp, rpc, 0, y_lo ? mx : nullptr));
+  GN_PARTIAL0(x_bf16, dim3(nchunk, (unsigned)N), 256, 0, st>>>(x, nullptr, nullptr, nullptr, part, S, C, C / G, G, txp, rpc, 0, y_lo ? mx : nullptr));
   gn_finalize_kernel<<<dim3((unsigned)N, gn_slices(C, G)), 256, 0, st>>>(part, nullptr, gamma, beta, ss, stats, cb, gb, S, C, G, nchunk, eps, mx, y_lo ? bound_rec : nullptr);
   int gx = stream_grid(S * (C / 8), 256);
   if (gx > 512) gx = 512;
@@ -716,8 +713,7 @@ extern "C" int wdno_groupnorm_act_add_fwd_planes_t(const void* x, int x_bf16, co
   const int txp = pow2ceil(C / 4);
   const int64_t rpc = cdiv64(S, nchunk);
   hipStream_t st = as_stream(s);
-  for (int rep_ = 0; rep_ < (wdno_debug_mode == 58 ? 2 : 1); ++rep_)
-    GN_PARTIAL0(x_bf16, dim3(nchunk, (unsigned)N), 256, 0, st>>>(x, nullptr, nullptr, nullptr, part, S, C, C / G, G, txp, rpc, 0, y_lo ? mx : nullptr));
+  GN_PARTIAL0(x_bf16, dim3(nchunk, (unsigned)N), 256, 0, st>>>(x, nullptr, nullptr, nullptr, part, S, C, C / G, G, txp, rpc, 0, y_lo ? mx : nullptr));
   gn_finalize_kernel<<<dim3((unsigned)N, gn_slices(C, G)), 256, 0, st>>>(part, nullptr, gamma, beta, ss, stats, cb, gb, S, C, G, nchunk, eps, mx, y_lo ? bound_rec : nullptr);
   int gx = stream_grid(S * (C / 8), 256);
   if (gx > 512) gx = 512;
@@ -791,8 +787,7 @@ extern "C" int wdno_groupnorm_act_bwd_planes_t(const void* x, int x_bf16, const 
     else if (dy_bf16) KERNEL(float, gn_bf16, __VA_ARGS__); else KERNEL(float, float, __VA_ARGS__); } while (0)
 #define GN_K_PARTIAL1(XT, DT, ...) gn_partial_kernel<1, XT, DT><<<dim3(nchunk, (unsigned)N), 256, 0, st>>>(__VA_ARGS__)
 #define GN_K_BWD_APPLY(XT, DT, ...) gn_bwd_apply_planes_kernel<XT, DT><<<dim3(gx, (unsigned)N), 256, 0, st>>>(__VA_ARGS__)
-  for (int rep_ = 0; rep_ < (wdno_debug_mode == 59 ? 2 : 1); ++rep_)
-    GN_BWD_TYPES(GN_K_PARTIAL1, x, dy, cb, gb, part, S, C, C / G, G, txp, rpc, silu, dx_lo ? mx : nullptr);
+  GN_BWD_TYPES(GN_K_PARTIAL1, x, dy, cb, gb, part, S, C, C / G, G, txp, rpc, silu, dx_lo ? mx : nullptr);
   gn_bwd_finalize_kernel<<<dim3((unsigned)N, gn_slices(C, G)), 256, 0, st>>>(part, gamma, beta, ss, gb, dgb_partial, dss, S, C, G, nchunk, cb, mx, dx_lo ? bound_rec : nullptr);
   const int gx = gn_planes_grid(N, S, C);
   GN_BWD_TYPES(GN_K_BWD_APPLY, x, dy, cb, gb, (_Float16*)dx_hi, (_Float16*)dx_lo, dx_scale, bound_rec, csp, S, C, C / G, G, silu);

@@ -1,7 +1,6 @@
 // pointwise.hip -- HBM-bound elementwise, layout and reduction kernels (gfx950).
 // All kernels are grid-stride with 16-byte accesses where the layout allows it.
 #include "common.h"
-extern int wdno_debug_mode;      // api.cpp (WDNO_DEBUG)
 
 // ---------------------------------------------------------------------------------------------- activations
 template <int ACT>
@@ -355,7 +354,7 @@ __global__ __launch_bounds__(256) void colsum_rows_kernel(const float* __restric
 extern "C" size_t wdno_colsum_ws_bytes(int64_t P, int C) { return (size_t)colsum_blocks(P) * (size_t)C * sizeof(double); }
 extern "C" int wdno_colsum(const float* in, float* out, int64_t P, int C, void* ws, size_t ws_bytes, wdno_stream_t s) {
   WDNO_REQUIRE(P > 0 && C > 0);
-  if (P <= 64 && wdno_debug_mode != 37) {          // debug 37: the two-launch path (A/B)
+  if (P <= 64) {
     colsum_rows_kernel<<<cdiv(C, 256), 256, 0, as_stream(s)>>>(in, out, (int)P, C);
     return wdno_check_launch();
   }
