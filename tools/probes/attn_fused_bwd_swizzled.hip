@@ -74,16 +74,6 @@ struct TFusedBwdP {
   int HW; float scale; int64_t nseq;
 };
 
-typedef short tb_short4 __attribute__((ext_vector_type(4)));
-typedef short tb_short8 __attribute__((ext_vector_type(8)));
-typedef tb_short4 __attribute__((address_space(3))) * tb_lds_s4;
-
-__device__ __forceinline__ half8 tb_tr2(const _Float16* p0, const _Float16* p1) {
-  const tb_short4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tb_lds_s4)(p0));
-  const tb_short4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tb_lds_s4)(p1));
-  const tb_short8 c = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(half8, c);
-}
 // LDS layouts (all conflict-free for BOTH access kinds they see -- profiles/r04_smoke_pmc.md had 1.4e7 SQ_LDS_BANK_CONFLICT per dispatch, all of
 // it from the transpose reads of the padded round-4 layouts):
 //   * W planes [384][64 halves] and the xn / dy images [24][64 halves]: rows of 128 B, the 16-byte chunk c of row r stored at chunk c ^ tb_sw(r).
@@ -107,7 +97,7 @@ __device__ __forceinline__ half8 tb_trf(const _Float16* img, int ch0, int lane, 
   const _Float16* p0 = img + tb_woff(row, col >> 3) + (col & 7);
   const _Float16* p1 = img + tb_woff(row + 4, col >> 3) + (col & 7);
   if (S == 1 && (g >> 1)) { p0 = zb; p1 = zb; }
-  return tb_tr2(p0, p1);
+  return tf_tr2(p0, p1);
 }
 // ... from a plane tile [24][32]: lane (li, hh) receives feature li of tokens 16 s + 8 hh + (0..7)
 template <int S>
@@ -117,7 +107,7 @@ __device__ __forceinline__ half8 tb_trp(const _Float16* tile, int lane, const _F
   const _Float16* p0 = tile + tb_poff(row, piece);
   const _Float16* p1 = tile + tb_poff(row + 4, piece);
   if (S == 1 && (g >> 1)) { p0 = zb; p1 = zb; }
-  return tb_tr2(p0, p1);
+  return tf_tr2(p0, p1);
 }
 // W^T fragment for dxn^T[c][tok] = sum_f W[f][c] d[tok][f]: lane (li, hh) receives channel 32 ct + li of the rows f0 + 4 hh + (0..3) and
 // f0 + 8 + 4 hh + (0..3) -- the features a lane half holds in accumulator registers 8 s .. 8 s + 7 when f0 = base + 16 s
@@ -125,18 +115,7 @@ __device__ __forceinline__ half8 tb_wtr(const _Float16* W, int f0, int ct, int l
   const int g = lane >> 4, xl = lane & 15;
   const int ra = f0 + 4 * (g >> 1) + (xl >> 2), rb = ra + 8;
   const int col = 32 * ct + 16 * (g & 1) + 4 * (xl & 3);
-  return tb_tr2(W + tb_woff(ra, col >> 3) + (col & 7), W + tb_woff(rb, col >> 3) + (col & 7));
-}
-__device__ __forceinline__ f32x16 tb_zero() {
-  f32x16 z;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) z[e] = 0.f;
-  return z;
-}
-__device__ __forceinline__ f32x16 tb_mfma3(half8 ah, half8 al, half8 bh, half8 bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
+  return tf_tr2(W + tb_woff(ra, col >> 3) + (col & 7), W + tb_woff(rb, col >> 3) + (col & 7));
 }
 // accumulator tile X^T[feature e][token li] -> fp32 tile [token][32] (tokens < 24)
 __device__ __forceinline__ void tb_acc_to_tile(float* __restrict__ T, const f32x16& v, int li, int hh) {
@@ -167,7 +146,7 @@ __device__ __forceinline__ void tb_rows(const float* __restrict__ T, int row, in
 // D^T[d][j] = sum_{token t < 24} a[t][d] b[t][j] on the exact-fp32 matrix instruction
 template <typename B>
 __device__ __forceinline__ f32x16 tb_product12(const float (&a)[12], const B& b) {
-  f32x16 acc = tb_zero();
+  f32x16 acc = tf_zero();
 #pragma unroll
   for (int m = 0; m < 12; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], b[m], acc, 0, 0, 0);
   return acc;
@@ -239,35 +218,7 @@ __device__ __forceinline__ void tb_unrotate(f32x16& v, const float2* __restrict_
     }
   }
 }
-// power-of-two plane scale for a tensor bounded by `bound`, kept inside [2^-100, 2^100]
-__device__ __forceinline__ float tb_scale(float bound) { return fminf(fmaxf(scale_from_amax(bound), 0x1p-100f), 0x1p100f); }
-
-// w *= r without a VALU instruction touching the accumulator (a value the VALU multiplies has to live in the architectural half of the
-// register file for its whole life -- 128 such registers spill) and IN PLACE (a fresh result tile merged back at the end of a rare branch
-// costs the allocator ~100 registers): sixteen accumulating steps of the exact-fp32 matrix instruction, step e adding (r - 1) * (the two
-// rows accumulator register e holds) -- row operand (r - 1) * unit vector, column operand the accumulator register itself. One rounding
-// per entry (r is a power of two, (r - 1) w is not exactly representable): 2^-24 relative, a handful of times per launch.
-__device__ __forceinline__ void tb_rescale(f32x16& w, float r, int li, int hh) {
-  const float r1 = r - 1.0f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) w = __builtin_amdgcn_mfma_f32_32x32x2f32(li == tf_key(e, hh) ? r1 : 0.f, w[e], w, 0, 0, 0);
-}
-// a gradient tile larger than every one before it: the tensor's two weight-gradient tiles move to the new scale (exact: a power of two)
-__device__ __forceinline__ void tb_fit(float& sc, float amax, f32x16& w0, f32x16& w1, int li, int hh) {
-  const float need = tb_scale(amax);
-  if (need < sc) {
-    const float r = need / sc;
-    tb_rescale(w0, r, li, hh);
-    tb_rescale(w1, r, li, hh);
-    sc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(need)));
-  }
-}
-__device__ __forceinline__ float tb_absmax16(const f32x16& v) {
-  float m = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) m = fmaxf(m, fabsf(v[e]));
-  return m;
-}
+// (accumulator helpers, the split MFMA, the transpose-read pair, the running plane scales: attn_fused.h)
 
 // ABL: timing ablations (tools/tattn_ablate.sh, WDNO_TB_ABLATE, built with -DWDNO_TB_ABLATIONS): 1 = no weight-gradient / dxn products, 2 = no
 // score-sized fp32 products, 3 = no block barriers, 4 = 1 + 2, 5 = 4 without the projections (results are wrong in all of them)
@@ -316,7 +267,7 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
   const float wq_s = p.wq_scale[0], wo_s = p.wo_scale[0];
   const float inv_qkv = 1.0f / (ps * wq_s);
   // plane scales: dy and O fixed for the launch (exact maxima), dq / dk / dv running (powers of two, only ever decreasing)
-  const float sc_g = tb_scale(amax_record_read(p.rec_dy)), sc_o = tb_scale(amax_record_read(p.rec_v));
+  const float sc_g = tf_scale(amax_record_read(p.rec_dy)), sc_o = tf_scale(amax_record_read(p.rec_v));
   float sc_q = 0x1p100f, sc_k = 0x1p100f, sc_v = 0x1p100f;
   const float inv_do = 1.0f / (sc_g * wo_s);
   const int64_t fstride = (int64_t)p.HW * TF_C;
@@ -332,8 +283,8 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
 
   f32x16 dwq[3][2], dwo[2];
 #pragma unroll
-  for (int ti = 0; ti < 3; ++ti) { dwq[ti][0] = tb_zero(); dwq[ti][1] = tb_zero(); }
-  dwo[0] = tb_zero(); dwo[1] = tb_zero();
+  for (int ti = 0; ti < 3; ++ti) { dwq[ti][0] = tf_zero(); dwq[ti][1] = tf_zero(); }
+  dwo[0] = tf_zero(); dwo[1] = tf_zero();
   float dbacc[12];
 #pragma unroll
   for (int e = 0; e < 12; ++e) dbacc[e] = 0.f;
@@ -384,21 +335,21 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     }
     if (ABL != 3) __syncthreads();                                            // B1: planes of xn and dy
     // ---- (q | k | v)^T of this head, dO^T = W_out^T dy^T (this head's 32 columns)
-    f32x16 aq = tb_zero(), ak = tb_zero(), av = tb_zero(), dOT = tb_zero();
+    f32x16 aq = tf_zero(), ak = tf_zero(), av = tf_zero(), dOT = tf_zero();
 #pragma unroll
     for (int s = 0; s < (ABL == 5 ? 0 : 4); ++s) {
       const half8 bh = *reinterpret_cast<const half8*>(XH + xoff[s]);
       const half8 bl = *reinterpret_cast<const half8*>(XH + xoff[s] + xl_off);
       const int o0 = tb_woff(h * 32 + li, 2 * s + hh);                       // rows + 128, + 256: same swizzle term ((f >> 1) & 7 has period 16)
-      aq = tb_mfma3(*reinterpret_cast<const half8*>(WH + o0), *reinterpret_cast<const half8*>(WL + o0), bh, bl, aq);
-      ak = tb_mfma3(*reinterpret_cast<const half8*>(WH + o0 + TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + TF_HD * TF_C), bh, bl, ak);
-      av = tb_mfma3(*reinterpret_cast<const half8*>(WH + o0 + 2 * TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + 2 * TF_HD * TF_C), bh, bl, av);
+      aq = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0), *reinterpret_cast<const half8*>(WL + o0), bh, bl, aq);
+      ak = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0 + TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + TF_HD * TF_C), bh, bl, ak);
+      av = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0 + 2 * TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + 2 * TF_HD * TF_C), bh, bl, av);
     }
 #pragma unroll
     for (int s = 0; s < (ABL == 5 ? 0 : 4); ++s) {
       const half8 bh = *reinterpret_cast<const half8*>(XH + xoff[s] + g_off);
       const half8 bl = *reinterpret_cast<const half8*>(XH + xoff[s] + g_off + xl_off);
-      dOT = tb_mfma3(woth[s], wotl[s], bh, bl, dOT);
+      dOT = tf_mfma3(woth[s], wotl[s], bh, bl, dOT);
     }
 #pragma unroll
     for (int e = 0; e < 16; ++e) { aq[e] *= inv_qkv; ak[e] *= inv_qkv; av[e] *= inv_qkv; dOT[e] *= inv_do; }
@@ -421,7 +372,7 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     }
     TB_FENCE();
     // ---- S^T = K Q^T and dP^T = V dO^T (exact fp32, operands in place); under them: the columns of v, then T0 = k
-    f32x16 sT = tb_zero(), dsT = tb_zero();
+    f32x16 sT = tf_zero(), dsT = tf_zero();
     float cv[12];
     tb_cols(T0, li, hh, cv);
     TB_FENCE();
@@ -488,7 +439,7 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     // ---- dK'^T = Q'^T dS; under it: dq un-rotated, its planes
     f32x16 dk = (ABL == 2 || ABL >= 4) ? dsT : tb_product12(cq, rS);
     tb_unrotate(dq, Rt, li, hh, p.scale);
-    tb_fit(sc_q, tf_wave_max(tb_absmax16(dq)), dwq[0][0], dwq[0][1], li, hh);
+    tf_fit(sc_q, tf_wave_max(tf_absmax16(dq)), dwq[0][0], dwq[0][1], li, hh);
     half8 qh[2], ql[2];
     tb_split16(dq, sc_q, qh, ql, PH, PL, li, hh);                              // (after the reads of O's planes: LDS keeps a wave's order)
     TB_FENCE();
@@ -496,8 +447,8 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     if (ABL != 1 && ABL < 4) {
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) {
-        dwo[ct] = tb_mfma3(tb_trf<0>(GH, 32 * ct, lane, ZB), tb_trf<0>(GL, 32 * ct, lane, ZB), bo_h[0], bo_l[0], dwo[ct]);
-        dwo[ct] = tb_mfma3(tb_trf<1>(GH, 32 * ct, lane, ZB), tb_trf<1>(GL, 32 * ct, lane, ZB), bo_h[1], bo_l[1], dwo[ct]);
+        dwo[ct] = tf_mfma3(tb_trf<0>(GH, 32 * ct, lane, ZB), tb_trf<0>(GL, 32 * ct, lane, ZB), bo_h[0], bo_l[0], dwo[ct]);
+        dwo[ct] = tf_mfma3(tb_trf<1>(GH, 32 * ct, lane, ZB), tb_trf<1>(GL, 32 * ct, lane, ZB), bo_h[1], bo_l[1], dwo[ct]);
       }
     }
     // the rows of this sequence again (for the LayerNorm backward and the residual gradient) and those of the next one: in flight from here
@@ -506,21 +457,21 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     if (seq + gridDim.x < p.nseq) fetch((int64_t)nb * TF_NT * p.HW + npix, nx0, nx1, ng0, ng1);
     // ---- dV^T = dO^T P; under it: the operands of dW_q / dxn_q
     f32x16 dv = (ABL == 2 || ABL >= 4) ? sT : tb_product12(cdo, rP);
-    f32x16 dxs0 = tb_zero(), dxs1 = tb_zero();                                // dxn^T of this head, channels 0..31 / 32..63 (fp32 sum of the three tensors' parts)
+    f32x16 dxs0 = tf_zero(), dxs1 = tf_zero();                                // dxn^T of this head, channels 0..31 / 32..63 (fp32 sum of the three tensors' parts)
     // weight-gradient tiles  dW[feature][32 ct + c] += sum_tok P[tok][feature] xn[tok][c]  and  dxn^T[c][tok] += sum_f W[f][c] d[tok][f]
     auto grad_products = [&](f32x16& w0, f32x16& w1, float sc, int fbase, const half8 (&dh)[2], const half8 (&dl)[2]) {
       if (ABL == 1 || ABL >= 4) return;
-      f32x16 d0 = tb_zero(), d1 = tb_zero();
+      f32x16 d0 = tf_zero(), d1 = tf_zero();
       const half8 a0h = tb_trp<0>(PH, lane, ZB), a0l = tb_trp<0>(PL, lane, ZB);
       const half8 a1h = tb_trp<1>(PH, lane, ZB), a1l = tb_trp<1>(PL, lane, ZB);
-      w0 = tb_mfma3(a0h, a0l, tb_trf<0>(XH, 0, lane, ZB), tb_trf<0>(XL, 0, lane, ZB), w0);
-      w0 = tb_mfma3(a1h, a1l, tb_trf<1>(XH, 0, lane, ZB), tb_trf<1>(XL, 0, lane, ZB), w0);
-      w1 = tb_mfma3(a0h, a0l, tb_trf<0>(XH, 32, lane, ZB), tb_trf<0>(XL, 32, lane, ZB), w1);
-      w1 = tb_mfma3(a1h, a1l, tb_trf<1>(XH, 32, lane, ZB), tb_trf<1>(XL, 32, lane, ZB), w1);
+      w0 = tf_mfma3(a0h, a0l, tb_trf<0>(XH, 0, lane, ZB), tb_trf<0>(XL, 0, lane, ZB), w0);
+      w0 = tf_mfma3(a1h, a1l, tb_trf<1>(XH, 0, lane, ZB), tb_trf<1>(XL, 0, lane, ZB), w0);
+      w1 = tf_mfma3(a0h, a0l, tb_trf<0>(XH, 32, lane, ZB), tb_trf<0>(XL, 32, lane, ZB), w1);
+      w1 = tf_mfma3(a1h, a1l, tb_trf<1>(XH, 32, lane, ZB), tb_trf<1>(XL, 32, lane, ZB), w1);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        d0 = tb_mfma3(tb_wtr(WH, fbase + 16 * s, 0, lane), tb_wtr(WL, fbase + 16 * s, 0, lane), dh[s], dl[s], d0);
-        d1 = tb_mfma3(tb_wtr(WH, fbase + 16 * s, 1, lane), tb_wtr(WL, fbase + 16 * s, 1, lane), dh[s], dl[s], d1);
+        d0 = tf_mfma3(tb_wtr(WH, fbase + 16 * s, 0, lane), tb_wtr(WL, fbase + 16 * s, 0, lane), dh[s], dl[s], d0);
+        d1 = tf_mfma3(tb_wtr(WH, fbase + 16 * s, 1, lane), tb_wtr(WL, fbase + 16 * s, 1, lane), dh[s], dl[s], d1);
       }
       const float inv = 1.0f / (sc * wq_s);
 #pragma unroll
@@ -529,12 +480,12 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     grad_products(dwq[0][0], dwq[0][1], sc_q, h * 32, qh, ql);
     TB_FENCE();
     tb_unrotate(dk, Rt, li, hh, 1.0f);
-    tb_fit(sc_k, tf_wave_max(tb_absmax16(dk)), dwq[1][0], dwq[1][1], li, hh);
+    tf_fit(sc_k, tf_wave_max(tf_absmax16(dk)), dwq[1][0], dwq[1][1], li, hh);
     tb_split16(dk, sc_k, qh, ql, PH, PL, li, hh);
     TB_FENCE();
     grad_products(dwq[1][0], dwq[1][1], sc_k, TF_HD + h * 32, qh, ql);
     TB_FENCE();
-    tb_fit(sc_v, tf_wave_max(tb_absmax16(dv)), dwq[2][0], dwq[2][1], li, hh);
+    tf_fit(sc_v, tf_wave_max(tf_absmax16(dv)), dwq[2][0], dwq[2][1], li, hh);
     tb_split16(dv, sc_v, qh, ql, PH, PL, li, hh);
     TB_FENCE();
     grad_products(dwq[2][0], dwq[2][1], sc_v, 2 * TF_HD + h * 32, qh, ql);
@@ -631,18 +582,7 @@ __global__ __launch_bounds__(256) void tattn_fused_reduce_kernel(const float* __
   }
 }
 
-static int tb_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
-extern "C" size_t wdno_tattn_fused_bwd_ws_bytes(void) { return (size_t)tb_num_cus() * TB_E * sizeof(float); }
+extern "C" size_t wdno_tattn_fused_bwd_ws_bytes(void) { return (size_t)wdno_num_cus() * TB_E * sizeof(float); }
 extern "C" int wdno_tattn_fused_bwd_grads(void) { return TB_E; }
 
 extern "C" int wdno_tattn_fused_bwd(const float* x, const float* dy, const float* gamma, float eps, const void* wq_hi, const void* wq_lo,
@@ -677,7 +617,7 @@ extern "C" int wdno_tattn_fused_bwd(const float* x, const float* dy, const float
 #endif
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS_BYTES) != hipSuccess) return WDNO_ELAUNCH;
   }
-  int64_t grid = tb_num_cus();
+  int64_t grid = wdno_num_cus();
   if (grid > p.nseq) grid = p.nseq;
   kern<<<(int)grid, 256, TB_LDS_BYTES, as_stream(s)>>>(p);
   int rc = wdno_check_launch();

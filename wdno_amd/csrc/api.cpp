@@ -18,6 +18,17 @@ extern "C" const char* wdno_strerror(int code) {
 extern "C" int wdno_version(void) { return 100; }
 extern "C" const char* wdno_last_hip_error(void) { return hipGetErrorString(wdno_tls_last_hip_error); }
 
+int wdno_num_cus() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
+    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  return n;
+}
+
 // kernel-selection switches for A/B measurements and tests (debug_modes.h is the list); 0 in production
 int wdno_debug_mode = WDNO_DBG_OFF;
 extern "C" int wdno_set_debug(int mode) {

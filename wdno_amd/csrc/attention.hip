@@ -7,10 +7,9 @@
 //    k^T v is a genuine dense contraction over thousands of tokens -> v_mfma_f32_32x32x2_f32, streamed from
 //    global memory (each lane supplies one k and one v element per MFMA); the per-token 32x32 mat-vecs run
 //    on the vector ALU with the context broadcast from LDS.
-#include "common.h"
+#include "attn_fused.h"      // tf_key: the key / feature an accumulator register of a lane half holds
 #include "debug_modes.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define DH 32
 #define KST 33
 
@@ -455,7 +454,6 @@ __device__ __forceinline__ const float* am_uniform(const float* p) {
   unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
   return reinterpret_cast<const float*>(((uint64_t)hi << 32) | lo);
 }
-__device__ __forceinline__ int am_key(int m, int hh) { return 8 * (m >> 2) + 4 * hh + (m & 3); }
 
 // Rows of one operand ([n][32] floats: q, k, v or dO of one head) -> LDS tile [32][AM_TS], loaded cooperatively (8 lanes
 // per 128-byte row, three passes for 24 rows), optionally scaled and rotated on the way; rows >= n are zero-filled.
@@ -515,7 +513,7 @@ __device__ __forceinline__ void am_softmax(f32x16& sT, const float* __restrict__
   float mx = -INFINITY;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int j = am_key(e, hh);
+    const int j = tf_key(e, hh);
     float v = sT[e];
     if (brow && tok && j < n) v += brow[j];
     v = j < n ? v : -INFINITY;
@@ -567,7 +565,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 4) void attn_fwd_mfma_kernel(const f
     float va[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
-      const int j = am_key(m, hh);
+      const int j = tf_key(m, hh);
       va[m] = j < n ? qb[(unsigned)j * tstride + (unsigned)(2 * p.HD + li)] : 0.f;
     }
     __builtin_amdgcn_wave_barrier();
@@ -638,7 +636,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_fwd_mfma64_kernel(const
     for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
-        const int j = 32 * jt + am_key(m, hh);
+        const int j = 32 * jt + tf_key(m, hh);
         va[jt][m] = j < n ? qb[(unsigned)j * tstride + (unsigned)(2 * p.HD + li)] : 0.f;
       }
     __builtin_amdgcn_wave_barrier();
@@ -666,7 +664,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_fwd_mfma64_kernel(const
       for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int j = 32 * jt + am_key(e, hh);
+          const int j = 32 * jt + tf_key(e, hh);
           float v = sT[jt][e];
           if (brow && tok && j < n) v += brow[j];
           v = j < n ? v : -INFINITY;
@@ -750,7 +748,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 3) void attn_fwd_mfma_tiled_kernel(c
       }
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
-        const int j = 32 * jt + am_key(m, hh);
+        const int j = 32 * jt + tf_key(m, hh);
         va[m] = j < n ? qb[(unsigned)j * tstride + (unsigned)(2 * p.HD + li)] : 0.f;
       }
       f32x16 sT;
@@ -761,7 +759,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 3) void attn_fwd_mfma_tiled_kernel(c
       float mx = -INFINITY;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const float v = 32 * jt + am_key(e, hh) < n ? sT[e] : -INFINITY;
+        const float v = 32 * jt + tf_key(e, hh) < n ? sT[e] : -INFINITY;
         sT[e] = v;
         mx = fmaxf(mx, v);
       }
@@ -845,17 +843,17 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
         v[4 * c] = v4.x * mul; v[4 * c + 1] = v4.y * mul; v[4 * c + 2] = v4.z * mul; v[4 * c + 3] = v4.w * mul;
       }
     };
-    // column d = li of the 16 tokens t0 + am_key(m, hh): what a lane feeds to a product over the tokens
+    // column d = li of the 16 tokens t0 + tf_key(m, hh): what a lane feeds to a product over the tokens
     auto col16 = [&](const float* base, unsigned stride, int t0, unsigned col0, float mul, float (&v)[16]) {
       if (STAGED) {
         const float* T = tile_of(base, col0) + t0 * ATT_TILED_TS + li;
 #pragma unroll
-        for (int m = 0; m < 16; ++m) v[m] = T[am_key(m, hh) * ATT_TILED_TS];
+        for (int m = 0; m < 16; ++m) v[m] = T[tf_key(m, hh) * ATT_TILED_TS];
         return;
       }
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
-        const int t = t0 + am_key(m, hh);
+        const int t = t0 + tf_key(m, hh);
         v[m] = t < n ? base[(unsigned)t * stride + col0 + li] * mul : 0.f;
       }
     };
@@ -900,7 +898,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
         float mx = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const float v = 32 * jt + am_key(e, hh) < n ? sT[e] : -INFINITY;
+          const float v = 32 * jt + tf_key(e, hh) < n ? sT[e] : -INFINITY;
           sT[e] = v;
           mx = fmaxf(mx, v);
         }
@@ -933,7 +931,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
         }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const float pe = 32 * jt + am_key(e, hh) < n ? expf(sT[e] - m_run) * inv_l : 0.f;
+          const float pe = 32 * jt + tf_key(e, hh) < n ? expf(sT[e] - m_run) * inv_l : 0.f;
           sT[e] = pe * (dpT[e] - delta);              // dS^T
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1182,7 +1180,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int j = am_key(e, hh);
+      const int j = tf_key(e, hh);
       St[j * AM_TS + li] = dsT[e];
       if (db_regs) dbacc[e] += dsT[e];                 // entries with li >= n or j >= n are never written out
       else if (dbias && tok && j < n) atomicAdd(&dBs[(h * n + li) * n + j], dsT[e]);
@@ -1227,7 +1225,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
     // P with the lane roles swapped, over the Q tile; dV^T[d][j] = sum_i dO[i][d] P[i][j] (dO columns are the one global re-read left)
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int e = 0; e < 16; ++e) Pt[am_key(e, hh) * AM_TS + li] = pT[e];
+    for (int e = 0; e < 16; ++e) Pt[tf_key(e, hh) * AM_TS + li] = pT[e];
     __builtin_amdgcn_wave_barrier();
     {
       f32x16 dv;
@@ -1270,7 +1268,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
       if (tok) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int j = am_key(e, hh);
+          const int j = tf_key(e, hh);
           if (j < n) part[(wave * n + li) * n + j] = dbacc[e];
         }
       }
@@ -1290,23 +1288,13 @@ static void attn_fwd_mfma64_launch(const float* qkv, const float* rot_cos, const
   if (nb > 4096) nb = 4096;
   attn_fwd_mfma64_kernel<<<(unsigned)nb, 64 * AM_WAVES, lds, st>>>(qkv, rot_cos, rot_sin, bias, out, p);
 }
-static int attn_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
 // Grid of the one-wave-per-item kernels: exactly the blocks that are RESIDENT together (blocks per CU x CUs), each wave walking over
 // its items with a grid stride. The first versions launched up to 4096 / 2048 blocks: several rounds of the resident set with the last
 // one partly empty (2048 blocks on 768 slots = 2.67 rounds), and waves with 3 or 4 items each (a 28 % imbalance at the 40 x 40
 // level); with 768 / 1024 blocks every wave gets 12-17 items, i.e. at most one item of imbalance.
 static int64_t attn_grid(int64_t items, int blocks_per_cu) {
   int64_t nb = (items + AM_WAVES - 1) / AM_WAVES;
-  const int64_t cap = (int64_t)blocks_per_cu * attn_num_cus();
+  const int64_t cap = (int64_t)blocks_per_cu * wdno_num_cus();
   return nb > cap ? cap : nb;
 }
 static int attn_fill(AttnP& p, const wdno_attn_desc* d, float scale, int threads) {
@@ -1432,7 +1420,7 @@ extern "C" int wdno_attn_bwd_amax(const float* qkv, const float* rot_cos, const 
   // more than 64 tokens without rotation / bias (the mid spatial block): key / query tiles on the exact-fp32 matrix instruction (WDNO_DBG_ATTN_BWD_ROWS: thread per row)
   if (n > 64 && n <= ATT_TILED_MAXTOK && !rot_cos && !bias && !dbias && out && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV && wdno_debug_mode != WDNO_DBG_ATTN_BWD_ROWS) {
     int64_t nb = p.n_items;
-    const int64_t cap = 2LL * attn_num_cus();
+    const int64_t cap = 2LL * wdno_num_cus();
     if (nb > cap) nb = cap;
     p.amax_rec = amax_rec;
     if (n <= ATT_TILED_STAGE) attn_bwd_mfma_tiled_kernel<true><<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, dout, dqkv, p);
@@ -1472,7 +1460,7 @@ static int attn_bwd_rows(const float* qkv, const float* rot_cos, const float* ro
     const size_t lds = ((size_t)2 * n * DH + 3 * n) * sizeof(float);
     (void)hipFuncSetAttribute((const void*)attn_bwd_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int64_t nb = p.n_items;
-    const int64_t cap = 4LL * attn_num_cus();
+    const int64_t cap = 4LL * wdno_num_cus();
     if (nb > cap) nb = cap;
     attn_bwd_big_kernel<<<(unsigned)nb, ATT_BIG_THREADS, lds, as_stream(s)>>>(qkv, out, dout, dqkv, p);
     return wdno_check_launch();
@@ -1659,7 +1647,7 @@ __global__ __launch_bounds__(256) void linattn_ctx_merge_kernel(const float* __r
 #define LA_MAXCHUNKS 16
 static int la_ctx_chunks(int64_t units, int heads, int n_tok) {
   const int64_t uh = units * heads;
-  int64_t c = (2 * (int64_t)attn_num_cus() + uh - 1) / uh;
+  int64_t c = (2 * (int64_t)wdno_num_cus() + uh - 1) / uh;
   if (c > n_tok / 128) c = n_tok / 128;
   if (c > LA_MAXCHUNKS) c = LA_MAXCHUNKS;
   if (c < 1) c = 1;
@@ -2072,7 +2060,7 @@ static int la_check(int64_t units, int n, int heads) {
 }
 // backward workspace: dctx [units,heads,32,32] + T [units,heads,32]
 extern "C" size_t wdno_linattn_ws_bytes(int64_t units, int heads) {
-  const size_t chunk_part = units * heads <= 2 * (int64_t)attn_num_cus() ? (size_t)units * heads * LA_MAXCHUNKS * DH * DH : 0;      // partial contexts of a chunked token range
+  const size_t chunk_part = units * heads <= 2 * (int64_t)wdno_num_cus() ? (size_t)units * heads * LA_MAXCHUNKS * DH * DH : 0;      // partial contexts of a chunked token range
   return ((size_t)units * heads * DH * DH + (size_t)units * heads * DH + chunk_part) * sizeof(float);
 }
 extern "C" int wdno_linattn_fwd(const float* qkv, float* out, float* kstats, float* ctx, int64_t units, int n_tok, int heads,
@@ -2118,7 +2106,7 @@ extern "C" int wdno_linattn_bwd_amax(const float* qkv, const float* dout, const 
   hipStream_t st = as_stream(s);
   float* dctx = (float*)ws;
   float* tvec = dctx + (size_t)units * heads * DH * DH;
-  float* cpart = ws_bytes >= wdno_linattn_ws_bytes(units, heads) && units * heads <= 2 * (int64_t)attn_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
+  float* cpart = ws_bytes >= wdno_linattn_ws_bytes(units, heads) && units * heads <= 2 * (int64_t)wdno_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
   la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, st);
   if (wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {            // else: the thread-per-token kernel
     const size_t lds2 = ((size_t)(2 + 4 * 3) * LAM_TILE + 3 * DH) * sizeof(float);
@@ -2147,7 +2135,7 @@ extern "C" int wdno_linattn_bwd_planes(const float* qkv, const float* dout, cons
   hipStream_t st = as_stream(s);
   float* dctx = (float*)ws;
   float* tvec = dctx + (size_t)units * heads * DH * DH;
-  float* cpart = ws_bytes >= wdno_linattn_ws_bytes(units, heads) && units * heads <= 2 * (int64_t)attn_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
+  float* cpart = ws_bytes >= wdno_linattn_ws_bytes(units, heads) && units * heads <= 2 * (int64_t)wdno_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
   la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, st);
   if (dqkv_lo) {
     rc = wdno_amax_record(dctx, (int64_t)units * heads * DH * DH, rec_dctx, s);

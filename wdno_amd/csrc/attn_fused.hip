@@ -21,6 +21,8 @@
 //   * to_out: the head's slice of the reduction (32 of 128) on the split MFMA again -- the accumulator registers of O^T are the
 //     B fragments once W_out's fragments are gathered in the matching feature order -- partial [64][token] tiles of the four heads
 //     summed through LDS together with the residual x (kept in registers by the lanes that loaded it), one coalesced store per row.
+// The steps (tf_ names) are written once in attn_fused.h and shared with the 48-frame, wide and backward kernels; here: the order of the
+// steps for 24 frames, the resident W_out fragments, the optional qkv_out / rec_v outputs, and the entry point that routes to the siblings.
 #include "attn_fused.h"
 
 
@@ -53,25 +55,10 @@ __global__ __launch_bounds__(256, 2) void tattn_fused_fwd_kernel(TFusedP p) {
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int off = (32 * ct + li) * TF_HD + 32 * h + 16 * s + 4 * hh;
-      const half4v a = *reinterpret_cast<const half4v*>(p.wo_hi + off), b = *reinterpret_cast<const half4v*>(p.wo_hi + off + 8);
-      const half4v c = *reinterpret_cast<const half4v*>(p.wo_lo + off), d = *reinterpret_cast<const half4v*>(p.wo_lo + off + 8);
-      woh[ct][s] = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-      wol[ct][s] = __builtin_shufflevector(c, d, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-  // rotary table in LDS as (cos, sin) pairs: entry [token][pair i] -> (cos, sin) of features (2 i, 2 i + 1); rows 24..31 = identity
-  for (int i = tid; i < 32 * 16; i += 256) {
-    const int t = i >> 4, j = i & 15;
-    float2 v = make_float2(1.f, 0.f);
-    if (p.rcos && t < TF_NT) v = make_float2(p.rcos[t * 32 + 2 * j], p.rsin[t * 32 + 2 * j]);
-    Rt[t * TF_RST + j] = v;
-  }
-  // relative-position bias [head][query][key] (zeros where absent / beyond the 24 tokens)
-  for (int i = tid; i < TF_HEADS * 32 * TF_BST; i += 256) {
-    const int hd = i / (32 * TF_BST), r = i - hd * (32 * TF_BST), q = r / TF_BST, k = r - q * TF_BST;
-    Bs[hd][r] = (p.bias && q < TF_NT && k < TF_NT) ? p.bias[(hd * TF_NT + q) * TF_NT + k] : 0.f;
-  }
+    for (int s = 0; s < 2; ++s) tf_wout_frag(p.wo_hi, p.wo_lo, ct, h, s, li, hh, woh[ct][s], wol[ct][s]);
+  // rotary (cos, sin) pairs (rows 24..31 = identity) and relative-position bias [head][query][key] in LDS
+  tf_rotary_table<32, TF_NT, 256>(Rt, p.rcos, p.rsin, tid);
+  tf_bias_table<32, TF_NT, TF_BST, 256>(&Bs[0][0], p.bias, tid);
   const float4 g4 = reinterpret_cast<const float4*>(p.gamma)[lc4];
   const float ps = scale_from_amax(8.0f * group_max<16>(amax4(0.f, g4)));        // |LayerNorm(x)| <= sqrt(64) max|g|
   const float inv_qkv = 1.0f / (ps * p.wq_scale[0]);
@@ -102,24 +89,7 @@ __global__ __launch_bounds__(256, 2) void tattn_fused_fwd_kernel(TFusedP p) {
     if (seq + gridDim.x < p.nseq) fetch((int64_t)nb * TF_NT * p.HW + npix);
     // ---- (q | k | v)^T of this head: [feature][token]
     f32x16 aq, ak, av;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { aq[e] = 0.f; ak[e] = 0.f; av[e] = 0.f; }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const half8 ah = *reinterpret_cast<const half8*>(Ah + li * TF_AST + 16 * s + 8 * hh);
-      const half8 al = *reinterpret_cast<const half8*>(Al + li * TF_AST + 16 * s + 8 * hh);
-      aq = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[0][s], al, aq, 0, 0, 0);
-      ak = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[1][s], al, ak, 0, 0, 0);
-      av = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[2][s], al, av, 0, 0, 0);
-      aq = __builtin_amdgcn_mfma_f32_32x32x16_f16(wql[0][s], ah, aq, 0, 0, 0);
-      ak = __builtin_amdgcn_mfma_f32_32x32x16_f16(wql[1][s], ah, ak, 0, 0, 0);
-      av = __builtin_amdgcn_mfma_f32_32x32x16_f16(wql[2][s], ah, av, 0, 0, 0);
-      aq = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[0][s], ah, aq, 0, 0, 0);
-      ak = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[1][s], ah, ak, 0, 0, 0);
-      av = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[2][s], ah, av, 0, 0, 0);
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { aq[e] *= inv_qkv; ak[e] *= inv_qkv; av[e] *= inv_qkv; }
+    tf_qkv_project(wqh, wql, Ah, Al, li, hh, inv_qkv, aq, ak, av);
     if (p.qkv_out && tok) {
       float* qr = p.qkv_out + (row0 + (int64_t)li * p.HW) * (3 * TF_HD) + h * 32 + 4 * hh;
 #pragma unroll
@@ -140,59 +110,18 @@ __global__ __launch_bounds__(256, 2) void tattn_fused_fwd_kernel(TFusedP p) {
     }
     stv = fmaxf(stv, amv);
     amv = tf_wave_max(amv);
-    // q * scale, rotary on q and k (pairs (2i, 2i + 1) = accumulator registers (2 j, 2 j + 1))
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      // features 8 c + 4 hh + (0..3) = pairs 4 c + 2 hh, 4 c + 2 hh + 1
-      const float4 r4 = *reinterpret_cast<const float4*>(Rt + li * TF_RST + 4 * c + 2 * hh);
-      const float cs2[2] = {r4.x, r4.z}, sn2[2] = {r4.y, r4.w};
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int j = 2 * c + q;
-        const float qx = aq[2 * j] * p.scale, qy = aq[2 * j + 1] * p.scale;
-        aq[2 * j] = qx * cs2[q] - qy * sn2[q];
-        aq[2 * j + 1] = qy * cs2[q] + qx * sn2[q];
-        const float kx = ak[2 * j], ky = ak[2 * j + 1];
-        ak[2 * j] = kx * cs2[q] - ky * sn2[q];
-        ak[2 * j + 1] = ky * cs2[q] + kx * sn2[q];
-      }
-    }
+    tf_rotary_qk(aq, ak, Rt, li, hh, p.scale);
     // ---- S^T = K Q^T (exact fp32), softmax over the keys of this lane's query
-    f32x16 sT;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) sT[e] = 0.f;
+    f32x16 sT = tf_zero();
 #pragma unroll
     for (int e = 0; e < 16; ++e) sT = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[e], aq[e], sT, 0, 0, 0);
-    {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {                     // keys 8 c + 4 hh + (0..3) < 24
-        const float4 b4 = *reinterpret_cast<const float4*>(Bs[h] + li * TF_BST + 8 * c + 4 * hh);
-        sT[4 * c] += b4.x; sT[4 * c + 1] += b4.y; sT[4 * c + 2] += b4.z; sT[4 * c + 3] += b4.w;
-        mx = fmaxf(fmaxf(mx, fmaxf(sT[4 * c], sT[4 * c + 1])), fmaxf(sT[4 * c + 2], sT[4 * c + 3]));
-      }
-      float m0, m1;
-      tf_halves(mx, m0, m1);
-      mx = fmaxf(m0, m1);
-      float l = 0.f;
-#pragma unroll
-      for (int e = 0; e < 12; ++e) { sT[e] = expf(sT[e] - mx); l += sT[e]; }
-#pragma unroll
-      for (int e = 12; e < 16; ++e) sT[e] = 0.f;            // keys 24 .. 31 do not exist
-      float l0, l1;
-      tf_halves(l, l0, l1);
-      const float il = 1.0f / (l0 + l1);
-#pragma unroll
-      for (int e = 0; e < 12; ++e) sT[e] *= il;
-    }
+    tf_softmax24(sT, Bs[h], li, hh);
     // ---- O^T = V^T P^T
     __builtin_amdgcn_wave_barrier();
     float va[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) va[m] = vt[tf_key(m, hh) * TF_VST + li];
-    f32x16 oT;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oT[e] = 0.f;
+    f32x16 oT = tf_zero();
 #pragma unroll
     for (int m = 0; m < 16; ++m) oT = __builtin_amdgcn_mfma_f32_32x32x2f32(va[m], sT[m], oT, 0, 0, 0);
     // the residual rows again (L2 hits; not held in registers across the products: the weight fragments own the register file)
@@ -202,71 +131,20 @@ __global__ __launch_bounds__(256, 2) void tattn_fused_fwd_kernel(TFusedP p) {
     // ---- to_out, this head's 32 of the 128 reduction values: y_part[c][token]
     const float so = scale_from_amax(amv);
     half8 oh[2], ol[2];
+    tf_split16(oT, so, oh, ol);
+    f32x16 y0 = tf_zero(), y1 = tf_zero();
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const float t = oT[e] * so;
-      const _Float16 th = (_Float16)t;
-      oh[e >> 3][e & 7] = th;
-      ol[e >> 3][e & 7] = (_Float16)(t - (float)th);
-    }
-    f32x16 y0, y1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { y0[e] = 0.f; y1[e] = 0.f; }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      y0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(woh[0][s], ol[s], y0, 0, 0, 0);
-      y1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(woh[1][s], ol[s], y1, 0, 0, 0);
-      y0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wol[0][s], oh[s], y0, 0, 0, 0);
-      y1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wol[1][s], oh[s], y1, 0, 0, 0);
-      y0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(woh[0][s], oh[s], y0, 0, 0, 0);
-      y1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(woh[1][s], oh[s], y1, 0, 0, 0);
-    }
+    for (int s = 0; s < 2; ++s) tf_to_out_step(woh[0][s], woh[1][s], wol[0][s], wol[1][s], oh[s], ol[s], y0, y1);
     const float inv_o = 1.0f / (so * sw_o);
-    if (tok) {
-      float* yp = Yp[h] + li * TF_YST + 4 * hh;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        *reinterpret_cast<float4*>(yp + 8 * c) = make_float4(y0[4 * c] * inv_o, y0[4 * c + 1] * inv_o, y0[4 * c + 2] * inv_o, y0[4 * c + 3] * inv_o);
-        *reinterpret_cast<float4*>(yp + 32 + 8 * c) = make_float4(y1[4 * c] * inv_o, y1[4 * c + 1] * inv_o, y1[4 * c + 2] * inv_o, y1[4 * c + 3] * inv_o);
-      }
-    }
+    if (tok) tf_partial_store(Yp[h] + li * TF_YST + 4 * hh, y0, y1, inv_o);
     __syncthreads();
     // ---- heads summed, residual added, rows stored (the lanes that loaded a row finish it)
     float* yb = p.y + row0 * TF_C;
-    {
-      const int o = lrow * TF_YST + 4 * lc4;
-      const float4 a = *reinterpret_cast<const float4*>(Yp[0] + o), b2 = *reinterpret_cast<const float4*>(Yp[1] + o);
-      const float4 c = *reinterpret_cast<const float4*>(Yp[2] + o), d = *reinterpret_cast<const float4*>(Yp[3] + o);
-      float4 r;
-      r.x = ((a.x + b2.x) + (c.x + d.x)) + x0.x; r.y = ((a.y + b2.y) + (c.y + d.y)) + x0.y;
-      r.z = ((a.z + b2.z) + (c.z + d.z)) + x0.z; r.w = ((a.w + b2.w) + (c.w + d.w)) + x0.w;
-      *reinterpret_cast<float4*>(yb + lrow * fstride + 4 * lc4) = r;
-      am = amax4(am, r);
-    }
-    if (lrow < 8) {
-      const int o = (16 + lrow) * TF_YST + 4 * lc4;
-      const float4 a = *reinterpret_cast<const float4*>(Yp[0] + o), b2 = *reinterpret_cast<const float4*>(Yp[1] + o);
-      const float4 c = *reinterpret_cast<const float4*>(Yp[2] + o), d = *reinterpret_cast<const float4*>(Yp[3] + o);
-      float4 r;
-      r.x = ((a.x + b2.x) + (c.x + d.x)) + x1.x; r.y = ((a.y + b2.y) + (c.y + d.y)) + x1.y;
-      r.z = ((a.z + b2.z) + (c.z + d.z)) + x1.z; r.w = ((a.w + b2.w) + (c.w + d.w)) + x1.w;
-      *reinterpret_cast<float4*>(yb + (16 + lrow) * fstride + 4 * lc4) = r;
-      am = amax4(am, r);
-    }
+    tf_head_sum_store(Yp[0], TF_NT * TF_YST, lrow, lc4, x0, yb, fstride, am);
+    if (lrow < 8) tf_head_sum_store(Yp[0], TF_NT * TF_YST, 16 + lrow, lc4, x1, yb, fstride, am);
   }
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * TF_HEADS + h);
   if (p.rec_v) wave_amax_emit(stv, p.rec_v, (int)blockIdx.x * TF_HEADS + h);
-}
-
-static int tf_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
 }
 
 // 24 frames: this file (and attn_fused_bwd.hip for the gradients); 48 frames: attn_fused48.hip, forward only
@@ -302,7 +180,7 @@ extern "C" int wdno_tattn_fused_fwd(const float* x, const float* gamma, float ep
     if (qkv_out) return WDNO_EUNSUPPORTED;          // (only the un-fused backward of the 24-frame block asks for the projections)
     return wdno_tattn_fused_fwd48_launch(p, as_stream(s));
   }
-  int64_t grid = 2 * (int64_t)tf_num_cus();
+  int64_t grid = 2 * (int64_t)wdno_num_cus();
   if (grid > p.nseq) grid = p.nseq;
   tattn_fused_fwd_kernel<<<(int)grid, 256, 0, as_stream(s)>>>(p);
   return wdno_check_launch();

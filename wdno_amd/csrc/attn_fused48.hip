@@ -14,6 +14,8 @@
 //   * to_out as attn_fused.hip; the partial [token][64] tiles of the four heads go through LDS (aliased onto the k / v tiles, which are
 //     dead by then), summed with the residual x by the threads that loaded the rows.
 // LDS 141 KB (planes 18, k + v tiles 74, rotary 9, bias 40): one block per CU, eight waves -- the occupancy of the 24-frame kernel.
+// Steps shared with the 24-frame kernel are the tf_ functions of attn_fused.h; t48_ / T48_ names are what only this file has: the two token
+// tiles per head, the exchange of k through LDS, the softmax over 48 keys, W_out fetched per sequence.
 #include "attn_fused.h"
 
 #define T48_NT 48
@@ -53,16 +55,8 @@ __global__ __launch_bounds__(512, 1) void tattn_fused_fwd48_kernel(TFusedP p) {
       wqh[ti][s] = *reinterpret_cast<const half8*>(p.wq_hi + off);
       wql[ti][s] = *reinterpret_cast<const half8*>(p.wq_lo + off);
     }
-  for (int i = tid; i < 64 * 16; i += 512) {
-    const int t = i >> 4, j = i & 15;
-    float2 v = make_float2(1.f, 0.f);
-    if (p.rcos && t < T48_NT) v = make_float2(p.rcos[t * 32 + 2 * j], p.rsin[t * 32 + 2 * j]);
-    Rt[t * TF_RST + j] = v;
-  }
-  for (int i = tid; i < TF_HEADS * T48_NT * T48_BST; i += 512) {
-    const int hd = i / (T48_NT * T48_BST), r = i - hd * (T48_NT * T48_BST), q = r / T48_BST, k = r - q * T48_BST;
-    Bs[i] = (p.bias && k < T48_NT) ? p.bias[(hd * T48_NT + q) * T48_NT + k] : 0.f;
-  }
+  tf_rotary_table<64, T48_NT, 512>(Rt, p.rcos, p.rsin, tid);
+  tf_bias_table<T48_NT, T48_NT, T48_BST, 512>(Bs, p.bias, tid);
   const float4 g4 = reinterpret_cast<const float4*>(p.gamma)[lc4];
   const float ps = scale_from_amax(8.0f * group_max<16>(amax4(0.f, g4)));        // |LayerNorm(x)| <= sqrt(64) max|g|
   const float inv_qkv = 1.0f / (ps * p.wq_scale[0]);
@@ -92,40 +86,8 @@ __global__ __launch_bounds__(512, 1) void tattn_fused_fwd48_kernel(TFusedP p) {
     if (seq + gridDim.x < p.nseq) fetch((int64_t)nb * T48_NT * p.HW + npix);
     // ---- (q | k | v)^T of this head and token tile: [feature][token]
     f32x16 aq, ak, av;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { aq[e] = 0.f; ak[e] = 0.f; av[e] = 0.f; }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const half8 ah = *reinterpret_cast<const half8*>(Ah + trow * TF_AST + 16 * s + 8 * hh);
-      const half8 al = *reinterpret_cast<const half8*>(Al + trow * TF_AST + 16 * s + 8 * hh);
-      aq = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[0][s], al, aq, 0, 0, 0);
-      ak = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[1][s], al, ak, 0, 0, 0);
-      av = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[2][s], al, av, 0, 0, 0);
-      aq = __builtin_amdgcn_mfma_f32_32x32x16_f16(wql[0][s], ah, aq, 0, 0, 0);
-      ak = __builtin_amdgcn_mfma_f32_32x32x16_f16(wql[1][s], ah, ak, 0, 0, 0);
-      av = __builtin_amdgcn_mfma_f32_32x32x16_f16(wql[2][s], ah, av, 0, 0, 0);
-      aq = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[0][s], ah, aq, 0, 0, 0);
-      ak = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[1][s], ah, ak, 0, 0, 0);
-      av = __builtin_amdgcn_mfma_f32_32x32x16_f16(wqh[2][s], ah, av, 0, 0, 0);
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { aq[e] *= inv_qkv; ak[e] *= inv_qkv; av[e] *= inv_qkv; }
-    // q * scale, rotary on q and k (pairs (2i, 2i + 1) = accumulator registers (2 j, 2 j + 1))
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float4 r4 = *reinterpret_cast<const float4*>(Rt + trow * TF_RST + 4 * c + 2 * hh);
-      const float cs2[2] = {r4.x, r4.z}, sn2[2] = {r4.y, r4.w};
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int j = 2 * c + q;
-        const float qx = aq[2 * j] * p.scale, qy = aq[2 * j + 1] * p.scale;
-        aq[2 * j] = qx * cs2[q] - qy * sn2[q];
-        aq[2 * j + 1] = qy * cs2[q] + qx * sn2[q];
-        const float kx = ak[2 * j], ky = ak[2 * j + 1];
-        ak[2 * j] = kx * cs2[q] - ky * sn2[q];
-        ak[2 * j + 1] = ky * cs2[q] + kx * sn2[q];
-      }
-    }
+    tf_qkv_project(wqh, wql, Ah, Al, trow, hh, inv_qkv, aq, ak, av);
+    tf_rotary_qk(aq, ak, Rt, trow, hh, p.scale);
     // k and v tiles of the head: [token][feature]; max|v| bounds |out| (rows of P sum to 1)
     float amv = 0.f;
     {
@@ -154,9 +116,7 @@ __global__ __launch_bounds__(512, 1) void tattn_fused_fwd48_kernel(TFusedP p) {
         ako[4 * c] = k4.x; ako[4 * c + 1] = k4.y; ako[4 * c + 2] = k4.z; ako[4 * c + 3] = k4.w;
       }
     }
-    f32x16 s0, s1;                                        // keys 0..31, keys 32..63
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { s0[e] = 0.f; s1[e] = 0.f; }
+    f32x16 s0 = tf_zero(), s1 = tf_zero();                // keys 0..31, keys 32..63
     if (tt == 0) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) s0 = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[e], aq[e], s0, 0, 0, 0);
@@ -201,9 +161,7 @@ __global__ __launch_bounds__(512, 1) void tattn_fused_fwd48_kernel(TFusedP p) {
       for (int e = 0; e < 8; ++e) s1[e] *= il;
     }
     // ---- O^T = V[0]^T P[0]^T + V[1]^T P[1]^T (keys 48..63 do not exist: eight steps of the second tile)
-    f32x16 oT;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oT[e] = 0.f;
+    f32x16 oT = tf_zero();
     {
       const float* v0 = Vt + h * 64 * TF_VST + li;
 #pragma unroll
@@ -219,82 +177,26 @@ __global__ __launch_bounds__(512, 1) void tattn_fused_fwd48_kernel(TFusedP p) {
     // the products they would not leave room for the second score tile)
     const float so = scale_from_amax(amv);
     half8 oh[2], ol[2];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const float t = oT[e] * so;
-      const _Float16 th = (_Float16)t;
-      oh[e >> 3][e & 7] = th;
-      ol[e >> 3][e & 7] = (_Float16)(t - (float)th);
-    }
-    f32x16 y0, y1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { y0[e] = 0.f; y1[e] = 0.f; }
+    tf_split16(oT, so, oh, ol);
+    f32x16 y0 = tf_zero(), y1 = tf_zero();
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       half8 woh[2], wol[2];
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-        // output channel 32 ct + li; reduction slot t of k-step s <-> feature 16 s + 8 (t >> 2) + 4 hh + (t & 3) of the head
-        const int off = (32 * ct + li) * TF_HD + 32 * h + 16 * s + 4 * hh;
-        const half4v a = *reinterpret_cast<const half4v*>(p.wo_hi + off), b = *reinterpret_cast<const half4v*>(p.wo_hi + off + 8);
-        const half4v c = *reinterpret_cast<const half4v*>(p.wo_lo + off), d = *reinterpret_cast<const half4v*>(p.wo_lo + off + 8);
-        woh[ct] = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-        wol[ct] = __builtin_shufflevector(c, d, 0, 1, 2, 3, 4, 5, 6, 7);
-      }
-      y0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(woh[0], ol[s], y0, 0, 0, 0);
-      y1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(woh[1], ol[s], y1, 0, 0, 0);
-      y0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wol[0], oh[s], y0, 0, 0, 0);
-      y1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wol[1], oh[s], y1, 0, 0, 0);
-      y0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(woh[0], oh[s], y0, 0, 0, 0);
-      y1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(woh[1], oh[s], y1, 0, 0, 0);
+      for (int ct = 0; ct < 2; ++ct) tf_wout_frag(p.wo_hi, p.wo_lo, ct, h, s, li, hh, woh[ct], wol[ct]);
+      tf_to_out_step(woh[0], woh[1], wol[0], wol[1], oh[s], ol[s], y0, y1);
     }
     const float inv_o = 1.0f / (so * sw_o);
     __syncthreads();                                                            // (3) every wave is done with the k / v tiles
-    if (tok) {
-      float* yp = Yp + (h * T48_NT + trow) * TF_YST + 4 * hh;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        *reinterpret_cast<float4*>(yp + 8 * c) = make_float4(y0[4 * c] * inv_o, y0[4 * c + 1] * inv_o, y0[4 * c + 2] * inv_o, y0[4 * c + 3] * inv_o);
-        *reinterpret_cast<float4*>(yp + 32 + 8 * c) = make_float4(y1[4 * c] * inv_o, y1[4 * c + 1] * inv_o, y1[4 * c + 2] * inv_o, y1[4 * c + 3] * inv_o);
-      }
-    }
+    if (tok) tf_partial_store(Yp + (h * T48_NT + trow) * TF_YST + 4 * hh, y0, y1, inv_o);
     __syncthreads();                                                            // (4) partial tiles
     // ---- heads summed, residual added, rows stored (the threads that loaded a row finish it)
     float* yb = p.y + row0 * TF_C;
-    {
-      const int o = lrow * TF_YST + 4 * lc4;
-      const float4 a = *reinterpret_cast<const float4*>(Yp + o), b2 = *reinterpret_cast<const float4*>(Yp + T48_NT * TF_YST + o);
-      const float4 c = *reinterpret_cast<const float4*>(Yp + 2 * T48_NT * TF_YST + o), d = *reinterpret_cast<const float4*>(Yp + 3 * T48_NT * TF_YST + o);
-      float4 r;
-      r.x = ((a.x + b2.x) + (c.x + d.x)) + x0.x; r.y = ((a.y + b2.y) + (c.y + d.y)) + x0.y;
-      r.z = ((a.z + b2.z) + (c.z + d.z)) + x0.z; r.w = ((a.w + b2.w) + (c.w + d.w)) + x0.w;
-      *reinterpret_cast<float4*>(yb + lrow * fstride + 4 * lc4) = r;
-      am = amax4(am, r);
-    }
-    if (lrow < 16) {
-      const int o = (32 + lrow) * TF_YST + 4 * lc4;
-      const float4 a = *reinterpret_cast<const float4*>(Yp + o), b2 = *reinterpret_cast<const float4*>(Yp + T48_NT * TF_YST + o);
-      const float4 c = *reinterpret_cast<const float4*>(Yp + 2 * T48_NT * TF_YST + o), d = *reinterpret_cast<const float4*>(Yp + 3 * T48_NT * TF_YST + o);
-      float4 r;
-      r.x = ((a.x + b2.x) + (c.x + d.x)) + x1.x; r.y = ((a.y + b2.y) + (c.y + d.y)) + x1.y;
-      r.z = ((a.z + b2.z) + (c.z + d.z)) + x1.z; r.w = ((a.w + b2.w) + (c.w + d.w)) + x1.w;
-      *reinterpret_cast<float4*>(yb + (32 + lrow) * fstride + 4 * lc4) = r;
-      am = amax4(am, r);
-    }
+    tf_head_sum_store(Yp, T48_NT * TF_YST, lrow, lc4, x0, yb, fstride, am);
+    if (lrow < 16) tf_head_sum_store(Yp, T48_NT * TF_YST, 32 + lrow, lc4, x1, yb, fstride, am);
   }
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * 8 + wave);
   if (p.rec_v) wave_amax_emit(stv, p.rec_v, (int)blockIdx.x * 8 + wave);
-}
-
-static int t48_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
 }
 
 // called by wdno_tattn_fused_fwd (attn_fused.hip) for n_tok == 48
@@ -304,7 +206,7 @@ int wdno_tattn_fused_fwd48_launch(const TFusedP& p, hipStream_t st) {
     if (hipFuncSetAttribute((const void*)tattn_fused_fwd48_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T48_LDS_BYTES) != hipSuccess) return WDNO_ELAUNCH;
     attr_done = true;
   }
-  int64_t grid = t48_num_cus();
+  int64_t grid = wdno_num_cus();
   if (grid > p.nseq) grid = p.nseq;
   tattn_fused_fwd48_kernel<<<(int)grid, 512, T48_LDS_BYTES, st>>>(p);
   return wdno_check_launch();

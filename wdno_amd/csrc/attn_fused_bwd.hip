@@ -30,11 +30,13 @@
 //     operand, planes).
 //   * Every block writes ONE partial [dW_qkv | dW_out | dgamma | dbias]; tattn_fused_reduce_kernel adds the partials in block order
 //     (bit-reproducible: no atomics anywhere).
+// The recompute chain uses the forward's steps from attn_fused.h (tf_ln_row, tf_rotary_table, tf_rotary_qk; the softmax keeps a variant with the
+// bias row in registers), and shares the transpose-read, split and running-scale helpers there with linattn_fused_bwd.hip. tb_ / TB_ names are what
+// only this file has: the 24-row images with the zero block (tb_trf), the fp32 tiles (tb_acc_to_tile, tb_cols, tb_rows, tb_product12), tb_unrotate.
 #include <stdlib.h>
 #include "attn_fused.h"
 
 #define TB_TS 36                      /* floats per row of an fp32 tile */
-#define TB_PS 36                      /* halves per row of a per-head plane tile */
 #define TB_N_WQ (3 * TF_HD * TF_C)    /* 24576 */
 #define TB_N_WO (TF_C * TF_HD)        /* 8192 */
 #define TB_OFF_WO TB_N_WQ
@@ -69,16 +71,6 @@ struct TFusedBwdP {
   int HW; float scale; int64_t nseq;
 };
 
-typedef short tb_short4 __attribute__((ext_vector_type(4)));
-typedef short tb_short8 __attribute__((ext_vector_type(8)));
-typedef tb_short4 __attribute__((address_space(3))) * tb_lds_s4;
-
-__device__ __forceinline__ half8 tb_tr2(const _Float16* p0, const _Float16* p1) {
-  const tb_short4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tb_lds_s4)(p0));
-  const tb_short4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tb_lds_s4)(p1));
-  const tb_short8 c = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(half8, c);
-}
 // operand fragment from a [token][channel] image of 24 rows: lane (li, hh) receives channel ch0 + li of tokens 16 s + 8 hh + (0..7)
 // (conv_h3.hip: tr_frag; inside a 16-lane group lanes 4 j .. 4 j + 3 point at the four 8-byte pieces of row j). Tokens 24 .. 31 -- the
 // upper lane half of step s = 1 -- come from the zero block.
@@ -88,28 +80,7 @@ __device__ __forceinline__ half8 tb_trf(const _Float16* tile, int stride, int ch
   const _Float16* p0 = tile + (16 * S + 8 * (g >> 1) + (xl >> 2)) * stride + ch0 + 16 * (g & 1) + 4 * (xl & 3);
   const _Float16* p1 = p0 + 4 * stride;
   if (S == 1 && (g >> 1)) { p0 = zb; p1 = zb; }
-  return tb_tr2(p0, p1);
-}
-// halves offset of the 16-byte chunk `chunk` of row f in a swizzled W plane
-__device__ __forceinline__ int tb_woff(int f, int chunk) { return f * TF_C + ((chunk ^ ((f >> 1) & 7)) << 3); }
-// W^T fragment for dxn^T[c][tok] = sum_f W[f][c] d[tok][f]: lane (li, hh) receives channel 32 ct + li of the rows f0 + 4 hh + (0..3) and
-// f0 + 8 + 4 hh + (0..3) -- the features a lane half holds in accumulator registers 8 s .. 8 s + 7 when f0 = base + 16 s
-__device__ __forceinline__ half8 tb_wtr(const _Float16* W, int f0, int ct, int lane) {
-  const int g = lane >> 4, xl = lane & 15;
-  const int ra = f0 + 4 * (g >> 1) + (xl >> 2), rb = ra + 8;
-  const int col = 32 * ct + 16 * (g & 1) + 4 * (xl & 3);
-  return tb_tr2(W + tb_woff(ra, col >> 3) + (col & 7), W + tb_woff(rb, col >> 3) + (col & 7));
-}
-__device__ __forceinline__ f32x16 tb_zero() {
-  f32x16 z;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) z[e] = 0.f;
-  return z;
-}
-__device__ __forceinline__ f32x16 tb_mfma3(half8 ah, half8 al, half8 bh, half8 bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
+  return tf_tr2(p0, p1);
 }
 // accumulator tile X^T[feature e][token li] -> fp32 tile [token][32] (tokens < 24)
 __device__ __forceinline__ void tb_acc_to_tile(float* __restrict__ T, const f32x16& v, int li, int hh) {
@@ -140,62 +111,10 @@ __device__ __forceinline__ void tb_rows(const float* __restrict__ T, int row, in
 // D^T[d][j] = sum_{token t < 24} a[t][d] b[t][j] on the exact-fp32 matrix instruction
 template <typename B>
 __device__ __forceinline__ f32x16 tb_product12(const float (&a)[12], const B& b) {
-  f32x16 acc = tb_zero();
+  f32x16 acc = tf_zero();
 #pragma unroll
   for (int m = 0; m < 12; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], b[m], acc, 0, 0, 0);
   return acc;
-}
-// the 16 accumulator values of a lane as (hi, lo) halves at scale s: k-step s' of a product that contracts over the features takes
-// elements 8 s' .. 8 s' + 7; also written as planes [token li][32 features] for the transpose reads of the weight-gradient products
-__device__ __forceinline__ void tb_split16(const f32x16& v, float s, half8 (&h)[2], half8 (&l)[2], _Float16* __restrict__ Ph, _Float16* __restrict__ Pl,
-                                           int li, int hh) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const float t = v[e] * s;
-    const _Float16 th = (_Float16)t;
-    h[e >> 3][e & 7] = th;
-    l[e >> 3][e & 7] = (_Float16)(t - (float)th);
-  }
-  if (li < TF_NT) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      half4v a, b;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { a[j] = h[c >> 1][4 * (c & 1) + j]; b[j] = l[c >> 1][4 * (c & 1) + j]; }
-      *reinterpret_cast<half4v*>(Ph + li * TB_PS + 8 * c + 4 * hh) = a;
-      *reinterpret_cast<half4v*>(Pl + li * TB_PS + 8 * c + 4 * hh) = b;
-    }
-  }
-}
-// LayerNorm of one row by its 16 lanes (norm.hip: layernorm_kernel), planes written, mean and 1/std returned
-__device__ __forceinline__ void tb_ln_row(float4 xv, float4 g, float eps, float ps, _Float16* __restrict__ Ah, _Float16* __restrict__ Al, int row, int c4,
-                                          float& mean, float& rstd) {
-  mean = tf_row16_sum((xv.x + xv.y) + (xv.z + xv.w)) * (1.0f / TF_C);
-  xv.x -= mean; xv.y -= mean; xv.z -= mean; xv.w -= mean;
-  const float var = tf_row16_sum((xv.x * xv.x + xv.y * xv.y) + (xv.z * xv.z + xv.w * xv.w)) * (1.0f / TF_C);
-  rstd = 1.0f / sqrtf(var + eps);
-  const float o[4] = {xv.x * rstd * g.x, xv.y * rstd * g.y, xv.z * rstd * g.z, xv.w * rstd * g.w};
-  half4v h, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float t = o[j] * ps;
-    h[j] = (_Float16)t;
-    l[j] = (_Float16)(t - (float)h[j]);
-  }
-  *reinterpret_cast<half4v*>(Ah + row * TF_AST + 4 * c4) = h;
-  *reinterpret_cast<half4v*>(Al + row * TF_AST + 4 * c4) = l;
-}
-__device__ __forceinline__ void tb_plane_row(float4 v, float s, _Float16* __restrict__ Ah, _Float16* __restrict__ Al, int row, int c4) {
-  const float o[4] = {v.x, v.y, v.z, v.w};
-  half4v h, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float t = o[j] * s;
-    h[j] = (_Float16)t;
-    l[j] = (_Float16)(t - (float)h[j]);
-  }
-  *reinterpret_cast<half4v*>(Ah + row * TF_AST + 4 * c4) = h;
-  *reinterpret_cast<half4v*>(Al + row * TF_AST + 4 * c4) = l;
 }
 // gradient of the rotation: accumulator pairs (2 j, 2 j + 1) of token li; table rows as in the forward
 __device__ __forceinline__ void tb_unrotate(f32x16& v, const float2* __restrict__ Rt, int li, int hh, float mul) {
@@ -211,35 +130,6 @@ __device__ __forceinline__ void tb_unrotate(f32x16& v, const float2* __restrict_
       v[2 * j + 1] = (gy * cs2[q] - gx * sn2[q]) * mul;
     }
   }
-}
-// power-of-two plane scale for a tensor bounded by `bound`, kept inside [2^-100, 2^100]
-__device__ __forceinline__ float tb_scale(float bound) { return fminf(fmaxf(scale_from_amax(bound), 0x1p-100f), 0x1p100f); }
-
-// w *= r without a VALU instruction touching the accumulator (a value the VALU multiplies has to live in the architectural half of the
-// register file for its whole life -- 128 such registers spill) and IN PLACE (a fresh result tile merged back at the end of a rare branch
-// costs the allocator ~100 registers): sixteen accumulating steps of the exact-fp32 matrix instruction, step e adding (r - 1) * (the two
-// rows accumulator register e holds) -- row operand (r - 1) * unit vector, column operand the accumulator register itself. One rounding
-// per entry (r is a power of two, (r - 1) w is not exactly representable): 2^-24 relative, a handful of times per launch.
-__device__ __forceinline__ void tb_rescale(f32x16& w, float r, int li, int hh) {
-  const float r1 = r - 1.0f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) w = __builtin_amdgcn_mfma_f32_32x32x2f32(li == tf_key(e, hh) ? r1 : 0.f, w[e], w, 0, 0, 0);
-}
-// a gradient tile larger than every one before it: the tensor's two weight-gradient tiles move to the new scale (exact: a power of two)
-__device__ __forceinline__ void tb_fit(float& sc, float amax, f32x16& w0, f32x16& w1, int li, int hh) {
-  const float need = tb_scale(amax);
-  if (need < sc) {
-    const float r = need / sc;
-    tb_rescale(w0, r, li, hh);
-    tb_rescale(w1, r, li, hh);
-    sc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(need)));
-  }
-}
-__device__ __forceinline__ float tb_absmax16(const f32x16& v) {
-  float m = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) m = fmaxf(m, fabsf(v[e]));
-  return m;
 }
 
 // ABL: timing ablations (tools/tattn_ablate.sh, WDNO_TB_ABLATE, built with -DWDNO_TB_ABLATIONS): 1 = no weight-gradient / dxn products, 2 = no
@@ -262,24 +152,19 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
   float* T0 = reinterpret_cast<float*>(tb_smem + TB_L_T + h * TB_HEAD_LDS);
   float* T1 = T0 + TF_NT * TB_TS;
   _Float16* PH = reinterpret_cast<_Float16*>(T1 + TF_NT * TB_TS);
-  _Float16* PL = PH + TF_NT * TB_PS;
+  _Float16* PL = PH + TF_NT * TF_PS;
   float* Yp = T0;                                          // [24][TF_YST] partial dxn of this head (6528 B of T0 + T1's 6912)
 
   // ---- once per kernel: W_qkv planes -> LDS, zeroed images, rotary table, W_out^T fragments, LayerNorm gain, plane scales
   for (int q = tid; q < 3 * TF_HD * 8; q += 256) {
     const int f = q >> 3, ch = q & 7;
-    const int dst = tb_woff(f, ch);
+    const int dst = tf_woff(f, ch);
     *reinterpret_cast<uint4*>(WH + dst) = *reinterpret_cast<const uint4*>(p.wq_hi + f * TF_C + ch * 8);
     *reinterpret_cast<uint4*>(WL + dst) = *reinterpret_cast<const uint4*>(p.wq_lo + f * TF_C + ch * 8);
   }
   for (int i = tid; i < (TB_LDS_BYTES - TB_L_XH) / 16; i += 256) reinterpret_cast<uint4*>(tb_smem + TB_L_XH)[i] = make_uint4(0u, 0u, 0u, 0u);
   __syncthreads();
-  for (int i = tid; i < 32 * 16; i += 256) {
-    const int t = i >> 4, j = i & 15;
-    float2 v = make_float2(1.f, 0.f);
-    if (p.rcos && t < TF_NT) v = make_float2(p.rcos[t * 32 + 2 * j], p.rsin[t * 32 + 2 * j]);
-    Rt[t * TF_RST + j] = v;
-  }
+  tf_rotary_table<32, TF_NT, 256>(Rt, p.rcos, p.rsin, tid);
   // dO^T[d][tok] = sum_c W_out[c][32 h + d] dy[tok][c]: the A fragment of k-step s = channels 16 s + 8 hh + (0..7) of row 32 h + li of
   // W_out^T, 16 bytes of the packed data-gradient operand; fetched per sequence (L1 / L2) -- 32 registers held for the whole kernel spill
   const _Float16* wot_h = p.wo_hi + (32 * h + li) * TF_C + 8 * hh;
@@ -289,7 +174,7 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
   const float wq_s = p.wq_scale[0], wo_s = p.wo_scale[0];
   const float inv_qkv = 1.0f / (ps * wq_s);
   // plane scales: dy and O fixed for the launch (exact maxima), dq / dk / dv running (powers of two, only ever decreasing)
-  const float sc_g = tb_scale(amax_record_read(p.rec_dy)), sc_o = tb_scale(amax_record_read(p.rec_v));
+  const float sc_g = tf_scale(amax_record_read(p.rec_dy)), sc_o = tf_scale(amax_record_read(p.rec_v));
   float sc_q = 0x1p100f, sc_k = 0x1p100f, sc_v = 0x1p100f;
   const float inv_do = 1.0f / (sc_g * wo_s);
   const int64_t fstride = (int64_t)p.HW * TF_C;
@@ -301,8 +186,8 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
 
   f32x16 dwq[3][2], dwo[2];
 #pragma unroll
-  for (int ti = 0; ti < 3; ++ti) { dwq[ti][0] = tb_zero(); dwq[ti][1] = tb_zero(); }
-  dwo[0] = tb_zero(); dwo[1] = tb_zero();
+  for (int ti = 0; ti < 3; ++ti) { dwq[ti][0] = tf_zero(); dwq[ti][1] = tf_zero(); }
+  dwo[0] = tf_zero(); dwo[1] = tf_zero();
   float dbacc[12];
 #pragma unroll
   for (int e = 0; e < 12; ++e) dbacc[e] = 0.f;
@@ -331,11 +216,11 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     // ---- rows -> LayerNorm -> planes of xn; planes of dy. Only (mean, 1/std) of the two rows stay in registers: x and dy are read again
     // (L2) for the last phase, together with the rows of the next sequence.
     float mean0, mean1 = 0.f, rs0, rs1 = 0.f;
-    tb_ln_row(nx0, g4, p.eps, ps, XH, XL, lrow, lc4, mean0, rs0);
-    tb_plane_row(ng0, sc_g, GH, GL, lrow, lc4);
+    tf_ln_row(nx0, g4, p.eps, ps, XH, XL, lrow, lc4, mean0, rs0);
+    tf_plane_row(ng0, sc_g, GH, GL, lrow, lc4);
     if (lrow < 8) {
-      tb_ln_row(nx1, g4, p.eps, ps, XH, XL, 16 + lrow, lc4, mean1, rs1);
-      tb_plane_row(ng1, sc_g, GH, GL, 16 + lrow, lc4);
+      tf_ln_row(nx1, g4, p.eps, ps, XH, XL, 16 + lrow, lc4, mean1, rs1);
+      tf_plane_row(ng1, sc_g, GH, GL, 16 + lrow, lc4);
     }
     // the bias rows of this lane's query (L1 / L2: 96 bytes per lane), wanted after the first score product
     float bs[12];
@@ -353,44 +238,29 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     }
     if (ABL != 3) __syncthreads();                                            // B1: planes of xn and dy
     // ---- (q | k | v)^T of this head, dO^T = W_out^T dy^T (this head's 32 columns)
-    f32x16 aq = tb_zero(), ak = tb_zero(), av = tb_zero(), dOT = tb_zero();
+    f32x16 aq = tf_zero(), ak = tf_zero(), av = tf_zero(), dOT = tf_zero();
 #pragma unroll
     for (int s = 0; s < (ABL == 5 ? 0 : 4); ++s) {
       const half8 bh = *reinterpret_cast<const half8*>(xrow + 16 * s);
       const half8 bl = *reinterpret_cast<const half8*>(xrow + xl_off + 16 * s);
-      const int o0 = tb_woff(h * 32 + li, 2 * s + hh);                       // rows + 128, + 256: same swizzle term ((f >> 1) & 7 has period 16)
-      aq = tb_mfma3(*reinterpret_cast<const half8*>(WH + o0), *reinterpret_cast<const half8*>(WL + o0), bh, bl, aq);
-      ak = tb_mfma3(*reinterpret_cast<const half8*>(WH + o0 + TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + TF_HD * TF_C), bh, bl, ak);
-      av = tb_mfma3(*reinterpret_cast<const half8*>(WH + o0 + 2 * TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + 2 * TF_HD * TF_C), bh, bl, av);
+      const int o0 = tf_woff(h * 32 + li, 2 * s + hh);                       // rows + 128, + 256: same swizzle term ((f >> 1) & 7 has period 16)
+      aq = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0), *reinterpret_cast<const half8*>(WL + o0), bh, bl, aq);
+      ak = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0 + TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + TF_HD * TF_C), bh, bl, ak);
+      av = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0 + 2 * TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + 2 * TF_HD * TF_C), bh, bl, av);
     }
 #pragma unroll
     for (int s = 0; s < (ABL == 5 ? 0 : 4); ++s) {
       const half8 bh = *reinterpret_cast<const half8*>(grow + 16 * s);
       const half8 bl = *reinterpret_cast<const half8*>(grow + xl_off + 16 * s);
-      dOT = tb_mfma3(woth[s], wotl[s], bh, bl, dOT);
+      dOT = tf_mfma3(woth[s], wotl[s], bh, bl, dOT);
     }
 #pragma unroll
     for (int e = 0; e < 16; ++e) { aq[e] *= inv_qkv; ak[e] *= inv_qkv; av[e] *= inv_qkv; dOT[e] *= inv_do; }
     tb_acc_to_tile(T0, av, li, hh);                                           // T0 = v
-    // q * scale, rotary on q and k
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float4 r4 = *reinterpret_cast<const float4*>(Rt + li * TF_RST + 4 * c + 2 * hh);
-      const float cs2[2] = {r4.x, r4.z}, sn2[2] = {r4.y, r4.w};
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int j = 2 * c + q;
-        const float qx = aq[2 * j] * p.scale, qy = aq[2 * j + 1] * p.scale;
-        aq[2 * j] = qx * cs2[q] - qy * sn2[q];
-        aq[2 * j + 1] = qy * cs2[q] + qx * sn2[q];
-        const float kx = ak[2 * j], ky = ak[2 * j + 1];
-        ak[2 * j] = kx * cs2[q] - ky * sn2[q];
-        ak[2 * j + 1] = ky * cs2[q] + kx * sn2[q];
-      }
-    }
+    tf_rotary_qk(aq, ak, Rt, li, hh, p.scale);
     TB_FENCE();
     // ---- S^T = K Q^T and dP^T = V dO^T (exact fp32, operands in place); under them: the columns of v, then T0 = k
-    f32x16 sT = tb_zero(), dsT = tb_zero();
+    f32x16 sT = tf_zero(), dsT = tf_zero();
     float cv[12];
     tb_cols(T0, li, hh, cv);
     TB_FENCE();
@@ -399,7 +269,7 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     for (int e = 0; e < 16; ++e) if (!(ABL == 2 || ABL >= 4)) sT = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[e], aq[e], sT, 0, 0, 0);
 #pragma unroll
     for (int e = 0; e < 16; ++e) if (!(ABL == 2 || ABL >= 4)) dsT = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], dOT[e], dsT, 0, 0, 0);
-    {
+    {      // tf_softmax24 with the bias row held in registers (requested from global memory before the products; no LDS table here)
       float mx = -INFINITY;
 #pragma unroll
       for (int e = 0; e < 12; ++e) { sT[e] += bs[e]; mx = fmaxf(mx, sT[e]); }
@@ -445,11 +315,11 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     // ---- dQ'^T = K'^T dS^T; under it: the planes of O
     f32x16 dq = (ABL == 2 || ABL >= 4) ? dsT : tb_product12(ck, dsT);
     half8 oh[2], ol[2];
-    tb_split16(oT, sc_o, oh, ol, PH, PL, li, hh);
+    tf_split16<TF_NT>(oT, sc_o, oh, ol, PH, PL, li, hh);
     TB_FENCE();
     half8 bo_h[2], bo_l[2];
-    bo_h[0] = tb_trf<0>(PH, TB_PS, 0, lane, ZB); bo_l[0] = tb_trf<0>(PL, TB_PS, 0, lane, ZB);
-    bo_h[1] = tb_trf<1>(PH, TB_PS, 0, lane, ZB); bo_l[1] = tb_trf<1>(PL, TB_PS, 0, lane, ZB);
+    bo_h[0] = tb_trf<0>(PH, TF_PS, 0, lane, ZB); bo_l[0] = tb_trf<0>(PL, TF_PS, 0, lane, ZB);
+    bo_h[1] = tb_trf<1>(PH, TF_PS, 0, lane, ZB); bo_l[1] = tb_trf<1>(PL, TF_PS, 0, lane, ZB);
     float cdo[12], rP[12];
     tb_cols(T0, li, hh, cdo);
     tb_rows(T1, trow, hh, rP);
@@ -457,16 +327,16 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     // ---- dK'^T = Q'^T dS; under it: dq un-rotated, its planes
     f32x16 dk = (ABL == 2 || ABL >= 4) ? dsT : tb_product12(cq, rS);
     tb_unrotate(dq, Rt, li, hh, p.scale);
-    tb_fit(sc_q, tf_wave_max(tb_absmax16(dq)), dwq[0][0], dwq[0][1], li, hh);
+    tf_fit(sc_q, tf_wave_max(tf_absmax16(dq)), dwq[0][0], dwq[0][1], li, hh);
     half8 qh[2], ql[2];
-    tb_split16(dq, sc_q, qh, ql, PH, PL, li, hh);                              // (after the reads of O's planes: LDS keeps a wave's order)
+    tf_split16<TF_NT>(dq, sc_q, qh, ql, PH, PL, li, hh);                              // (after the reads of O's planes: LDS keeps a wave's order)
     TB_FENCE();
     // ---- dW_out[c][32 h + d] += sum_tok dy[tok][c] O[tok][d]: rows = channels (A = dy image), columns = d (B = the O planes)
     if (ABL != 1 && ABL < 4) {
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) {
-        dwo[ct] = tb_mfma3(tb_trf<0>(GH, TF_AST, 32 * ct, lane, ZB), tb_trf<0>(GL, TF_AST, 32 * ct, lane, ZB), bo_h[0], bo_l[0], dwo[ct]);
-        dwo[ct] = tb_mfma3(tb_trf<1>(GH, TF_AST, 32 * ct, lane, ZB), tb_trf<1>(GL, TF_AST, 32 * ct, lane, ZB), bo_h[1], bo_l[1], dwo[ct]);
+        dwo[ct] = tf_mfma3(tb_trf<0>(GH, TF_AST, 32 * ct, lane, ZB), tb_trf<0>(GL, TF_AST, 32 * ct, lane, ZB), bo_h[0], bo_l[0], dwo[ct]);
+        dwo[ct] = tf_mfma3(tb_trf<1>(GH, TF_AST, 32 * ct, lane, ZB), tb_trf<1>(GL, TF_AST, 32 * ct, lane, ZB), bo_h[1], bo_l[1], dwo[ct]);
       }
     }
     // the rows of this sequence again (for the LayerNorm backward and the residual gradient) and those of the next one: in flight from here
@@ -475,21 +345,21 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     if (seq + gridDim.x < p.nseq) fetch((int64_t)nb * TF_NT * p.HW + npix, nx0, nx1, ng0, ng1);
     // ---- dV^T = dO^T P; under it: the operands of dW_q / dxn_q
     f32x16 dv = (ABL == 2 || ABL >= 4) ? sT : tb_product12(cdo, rP);
-    f32x16 dxs0 = tb_zero(), dxs1 = tb_zero();                                // dxn^T of this head, channels 0..31 / 32..63 (fp32 sum of the three tensors' parts)
+    f32x16 dxs0 = tf_zero(), dxs1 = tf_zero();                                // dxn^T of this head, channels 0..31 / 32..63 (fp32 sum of the three tensors' parts)
     // weight-gradient tiles  dW[feature][32 ct + c] += sum_tok P[tok][feature] xn[tok][c]  and  dxn^T[c][tok] += sum_f W[f][c] d[tok][f]
     auto grad_products = [&](f32x16& w0, f32x16& w1, float sc, int fbase, const half8 (&dh)[2], const half8 (&dl)[2]) {
       if (ABL == 1 || ABL >= 4) return;
-      f32x16 d0 = tb_zero(), d1 = tb_zero();
-      const half8 a0h = tb_trf<0>(PH, TB_PS, 0, lane, ZB), a0l = tb_trf<0>(PL, TB_PS, 0, lane, ZB);
-      const half8 a1h = tb_trf<1>(PH, TB_PS, 0, lane, ZB), a1l = tb_trf<1>(PL, TB_PS, 0, lane, ZB);
-      w0 = tb_mfma3(a0h, a0l, tb_trf<0>(XH, TF_AST, 0, lane, ZB), tb_trf<0>(XL, TF_AST, 0, lane, ZB), w0);
-      w0 = tb_mfma3(a1h, a1l, tb_trf<1>(XH, TF_AST, 0, lane, ZB), tb_trf<1>(XL, TF_AST, 0, lane, ZB), w0);
-      w1 = tb_mfma3(a0h, a0l, tb_trf<0>(XH, TF_AST, 32, lane, ZB), tb_trf<0>(XL, TF_AST, 32, lane, ZB), w1);
-      w1 = tb_mfma3(a1h, a1l, tb_trf<1>(XH, TF_AST, 32, lane, ZB), tb_trf<1>(XL, TF_AST, 32, lane, ZB), w1);
+      f32x16 d0 = tf_zero(), d1 = tf_zero();
+      const half8 a0h = tb_trf<0>(PH, TF_PS, 0, lane, ZB), a0l = tb_trf<0>(PL, TF_PS, 0, lane, ZB);
+      const half8 a1h = tb_trf<1>(PH, TF_PS, 0, lane, ZB), a1l = tb_trf<1>(PL, TF_PS, 0, lane, ZB);
+      w0 = tf_mfma3(a0h, a0l, tb_trf<0>(XH, TF_AST, 0, lane, ZB), tb_trf<0>(XL, TF_AST, 0, lane, ZB), w0);
+      w0 = tf_mfma3(a1h, a1l, tb_trf<1>(XH, TF_AST, 0, lane, ZB), tb_trf<1>(XL, TF_AST, 0, lane, ZB), w0);
+      w1 = tf_mfma3(a0h, a0l, tb_trf<0>(XH, TF_AST, 32, lane, ZB), tb_trf<0>(XL, TF_AST, 32, lane, ZB), w1);
+      w1 = tf_mfma3(a1h, a1l, tb_trf<1>(XH, TF_AST, 32, lane, ZB), tb_trf<1>(XL, TF_AST, 32, lane, ZB), w1);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        d0 = tb_mfma3(tb_wtr(WH, fbase + 16 * s, 0, lane), tb_wtr(WL, fbase + 16 * s, 0, lane), dh[s], dl[s], d0);
-        d1 = tb_mfma3(tb_wtr(WH, fbase + 16 * s, 1, lane), tb_wtr(WL, fbase + 16 * s, 1, lane), dh[s], dl[s], d1);
+        d0 = tf_mfma3(tf_wtr(WH, fbase + 16 * s, 0, lane), tf_wtr(WL, fbase + 16 * s, 0, lane), dh[s], dl[s], d0);
+        d1 = tf_mfma3(tf_wtr(WH, fbase + 16 * s, 1, lane), tf_wtr(WL, fbase + 16 * s, 1, lane), dh[s], dl[s], d1);
       }
       const float inv = 1.0f / (sc * wq_s);
 #pragma unroll
@@ -498,13 +368,13 @@ __global__ __launch_bounds__(256, 1) void tattn_fused_bwd_kernel(TFusedBwdP p) {
     grad_products(dwq[0][0], dwq[0][1], sc_q, h * 32, qh, ql);
     TB_FENCE();
     tb_unrotate(dk, Rt, li, hh, 1.0f);
-    tb_fit(sc_k, tf_wave_max(tb_absmax16(dk)), dwq[1][0], dwq[1][1], li, hh);
-    tb_split16(dk, sc_k, qh, ql, PH, PL, li, hh);
+    tf_fit(sc_k, tf_wave_max(tf_absmax16(dk)), dwq[1][0], dwq[1][1], li, hh);
+    tf_split16<TF_NT>(dk, sc_k, qh, ql, PH, PL, li, hh);
     TB_FENCE();
     grad_products(dwq[1][0], dwq[1][1], sc_k, TF_HD + h * 32, qh, ql);
     TB_FENCE();
-    tb_fit(sc_v, tf_wave_max(tb_absmax16(dv)), dwq[2][0], dwq[2][1], li, hh);
-    tb_split16(dv, sc_v, qh, ql, PH, PL, li, hh);
+    tf_fit(sc_v, tf_wave_max(tf_absmax16(dv)), dwq[2][0], dwq[2][1], li, hh);
+    tf_split16<TF_NT>(dv, sc_v, qh, ql, PH, PL, li, hh);
     TB_FENCE();
     grad_products(dwq[2][0], dwq[2][1], sc_v, 2 * TF_HD + h * 32, qh, ql);
     TB_FENCE();
@@ -600,18 +470,7 @@ __global__ __launch_bounds__(256) void tattn_fused_reduce_kernel(const float* __
   }
 }
 
-static int tb_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
-extern "C" size_t wdno_tattn_fused_bwd_ws_bytes(void) { return (size_t)tb_num_cus() * TB_E * sizeof(float); }
+extern "C" size_t wdno_tattn_fused_bwd_ws_bytes(void) { return (size_t)wdno_num_cus() * TB_E * sizeof(float); }
 extern "C" int wdno_tattn_fused_bwd_grads(void) { return TB_E; }
 
 extern "C" int wdno_tattn_fused_bwd(const float* x, const float* dy, const float* gamma, float eps, const void* wq_hi, const void* wq_lo,
@@ -646,7 +505,7 @@ extern "C" int wdno_tattn_fused_bwd(const float* x, const float* dy, const float
 #endif
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS_BYTES) != hipSuccess) return WDNO_ELAUNCH;
   }
-  int64_t grid = tb_num_cus();
+  int64_t grid = wdno_num_cus();
   if (grid > p.nseq) grid = p.nseq;
   kern<<<(int)grid, 256, TB_LDS_BYTES, as_stream(s)>>>(p);
   int rc = wdno_check_launch();

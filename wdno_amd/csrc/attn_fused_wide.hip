@@ -17,6 +17,8 @@
 //   * to_out: the four heads' O tiles go to LDS as (hi, lo) planes [token][128] under ONE scale (max|v| over the heads: rows of P sum to
 //     1); wave w then owns output channels w C/4 .. and contracts over all 128 features (k-step pair t = head t), W_out streamed like
 //     W_qkv; residual added and rows stored from the accumulator layout (a lane owns a token and 4-channel runs).
+// Shared with the other kernels through attn_fused.h: LayerNorm row (tf_ln_row_wide), tables, rotary, softmax, the waits of the streaming
+// loops. Only here: the streamed projection / to_out loops and the O planes of the four heads (TW_ names).
 #include "attn_fused.h"
 
 #define TW_OST 136    /* halves per token row of an O plane (128 features + 8: 272 B = conflict-free ds_read_b128 fragments) */
@@ -45,20 +47,9 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
   // ---- per-kernel tables: zero rows, rotary (cos, sin) pairs, relative-position bias
   for (int i = tid; i < AST; i += 256) { Ah[TF_NT * AST + i] = (_Float16)0.f; Al[TF_NT * AST + i] = (_Float16)0.f; }
   for (int i = tid; i < TW_OST; i += 256) { Oh[TF_NT * TW_OST + i] = (_Float16)0.f; Ol[TF_NT * TW_OST + i] = (_Float16)0.f; }
-  for (int i = tid; i < 32 * 16; i += 256) {
-    const int t = i >> 4, j = i & 15;
-    float2 v = make_float2(1.f, 0.f);
-    if (p.rcos && t < TF_NT) v = make_float2(p.rcos[t * 32 + 2 * j], p.rsin[t * 32 + 2 * j]);
-    Rt[t * TF_RST + j] = v;
-  }
-  for (int i = tid; i < TF_HEADS * TF_NT * TF_BST; i += 256) {
-    const int hd = i / (TF_NT * TF_BST), r = i - hd * (TF_NT * TF_BST), q = r / TF_BST, k = r - q * TF_BST;
-    Bs[hd][r] = (p.bias && k < TF_NT) ? p.bias[(hd * TF_NT + q) * TF_NT + k] : 0.f;
-  }
-  float gm = 0.f;        // (the gain is re-read per row -- L1 hits -- rather than held across the matrix phases: registers)
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) gm = amax4(gm, reinterpret_cast<const float4*>(p.gamma)[16 * j + lc4]);
-  const float ps = scale_from_amax(sqrtf((float)C) * group_max<16>(gm));        // |LayerNorm(x)| <= sqrt(C) max|g|
+  tf_rotary_table<32, TF_NT, 256>(Rt, p.rcos, p.rsin, tid);
+  tf_bias_table<TF_NT, TF_NT, TF_BST, 256>(&Bs[0][0], p.bias, tid);
+  const float ps = tf_plane_scale_wide<C>(p.gamma, lc4);
   const float inv_qkv = 1.0f / (ps * p.wq_scale[0]);
   const float sw_o = p.wo_scale[0];
   const int64_t fstride = (int64_t)p.HW * C;
@@ -81,34 +72,6 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
       if (lrow < 8) nx1[j] = *reinterpret_cast<const float4*>(xr + (16 + lrow) * fstride + 64 * j + 4 * lc4);
     }
   };
-  auto ln_row = [&](const float4 (&xin)[NJ], int row) {
-    float4 xv[NJ];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { xv[j] = xin[j]; s += (xv[j].x + xv[j].y) + (xv[j].z + xv[j].w); }
-    const float mean = tf_row16_sum(s) * (1.0f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      xv[j].x -= mean; xv[j].y -= mean; xv[j].z -= mean; xv[j].w -= mean;
-      q += (xv[j].x * xv[j].x + xv[j].y * xv[j].y) + (xv[j].z * xv[j].z + xv[j].w * xv[j].w);
-    }
-    const float rstd = 1.0f / sqrtf(tf_row16_sum(q) * (1.0f / C) + p.eps);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const float4 g = reinterpret_cast<const float4*>(p.gamma)[16 * j + lc4];
-      const float o[4] = {xv[j].x * rstd * g.x, xv[j].y * rstd * g.y, xv[j].z * rstd * g.z, xv[j].w * rstd * g.w};
-      half4v hv, lv;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float t = o[e] * ps;
-        hv[e] = (_Float16)t;
-        lv[e] = (_Float16)(t - (float)hv[e]);
-      }
-      *reinterpret_cast<half4v*>(Ah + row * AST + 64 * j + 4 * lc4) = hv;
-      *reinterpret_cast<half4v*>(Al + row * AST + 64 * j + 4 * lc4) = lv;
-    }
-  };
 
   int nb = (int)(blockIdx.x / (unsigned)p.HW), npix = (int)(blockIdx.x - (unsigned)nb * (unsigned)p.HW);
   const int gstep_b = (int)(gridDim.x / (unsigned)p.HW), gstep_p = (int)(gridDim.x - (unsigned)gstep_b * (unsigned)p.HW);
@@ -117,8 +80,8 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
     const int64_t row0 = (int64_t)nb * TF_NT * p.HW + npix;      // row of frame 0; frame f at + f * HW
     nb += gstep_b; npix += gstep_p;
     if (npix >= p.HW) { npix -= p.HW; ++nb; }
-    ln_row(nx0, lrow);
-    if (lrow < 8) ln_row(nx1, 16 + lrow);
+    tf_ln_row_wide<C>(nx0, p.gamma, p.eps, ps, Ah, Al, lrow, lc4);
+    if (lrow < 8) tf_ln_row_wide<C>(nx1, p.gamma, p.eps, ps, Ah, Al, 16 + lrow, lc4);
     __syncthreads();                                                                  // S1: planes of this sequence complete
     // ---- (q | k | v)^T of this head: [feature][token], weight fragments streamed (double-buffered by pair)
     f32x16 aq, ak, av;
@@ -156,10 +119,8 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
       for (int t = 0; t < NP; t += 2) {        // both sets requested, waited for in full, consumed (attn_fused.h: the hand-over note)
         wload(w0h, w0l, t);
         wload(w1h, w1l, t + 1);
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(w0h[0][0]), "+v"(w0h[0][1]), "+v"(w0h[1][0]), "+v"(w0h[1][1]), "+v"(w0h[2][0]), "+v"(w0h[2][1]),
-                     "+v"(w0l[0][0]), "+v"(w0l[0][1]), "+v"(w0l[1][0]), "+v"(w0l[1][1]), "+v"(w0l[2][0]), "+v"(w0l[2][1]) :: "memory");
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(w1h[0][0]), "+v"(w1h[0][1]), "+v"(w1h[1][0]), "+v"(w1h[1][1]), "+v"(w1h[2][0]), "+v"(w1h[2][1]),
-                     "+v"(w1l[0][0]), "+v"(w1l[0][1]), "+v"(w1l[1][0]), "+v"(w1l[1][1]), "+v"(w1l[2][0]), "+v"(w1l[2][1]) :: "memory");
+        TF_WAIT_SET12(w0h[0][0], w0h[0][1], w0h[1][0], w0h[1][1], w0h[2][0], w0h[2][1], w0l[0][0], w0l[0][1], w0l[1][0], w0l[1][1], w0l[2][0], w0l[2][1]);
+        TF_WAIT_SET12(w1h[0][0], w1h[0][1], w1h[1][0], w1h[1][1], w1h[2][0], w1h[2][1], w1l[0][0], w1l[0][1], w1l[1][0], w1l[1][1], w1l[2][0], w1l[2][1]);
         wmma(w0h, w0l, t);
         wmma(w1h, w1l, t + 1);
         asm volatile("" : "+v"(aq), "+v"(ak), "+v"(av) :: "memory");
@@ -181,59 +142,18 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
     }
     amv = tf_wave_max(amv);
     if (lane == 0) Vmax[h] = amv;
-    // q * scale, rotary on q and k (pairs (2i, 2i + 1) = accumulator registers (2 j, 2 j + 1))
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float4 r4 = *reinterpret_cast<const float4*>(Rt + li * TF_RST + 4 * c + 2 * hh);
-      const float cs2[2] = {r4.x, r4.z}, sn2[2] = {r4.y, r4.w};
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int j = 2 * c + q;
-        const float qx = aq[2 * j] * p.scale, qy = aq[2 * j + 1] * p.scale;
-        aq[2 * j] = qx * cs2[q] - qy * sn2[q];
-        aq[2 * j + 1] = qy * cs2[q] + qx * sn2[q];
-        const float kx = ak[2 * j], ky = ak[2 * j + 1];
-        ak[2 * j] = kx * cs2[q] - ky * sn2[q];
-        ak[2 * j + 1] = ky * cs2[q] + kx * sn2[q];
-      }
-    }
+    tf_rotary_qk(aq, ak, Rt, li, hh, p.scale);
     // ---- S^T = K Q^T (exact fp32), softmax over the keys of this lane's query
-    f32x16 sT;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) sT[e] = 0.f;
+    f32x16 sT = tf_zero();
 #pragma unroll
     for (int e = 0; e < 16; ++e) sT = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[e], aq[e], sT, 0, 0, 0);
-    {
-      const int qb = tok ? li : TF_NT - 1;              // (columns of nonexistent queries are never stored)
-      float mx = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {                     // keys 8 c + 4 hh + (0..3) < 24
-        const float4 b4 = *reinterpret_cast<const float4*>(Bs[h] + qb * TF_BST + 8 * c + 4 * hh);
-        sT[4 * c] += b4.x; sT[4 * c + 1] += b4.y; sT[4 * c + 2] += b4.z; sT[4 * c + 3] += b4.w;
-        mx = fmaxf(fmaxf(mx, fmaxf(sT[4 * c], sT[4 * c + 1])), fmaxf(sT[4 * c + 2], sT[4 * c + 3]));
-      }
-      float m0, m1;
-      tf_halves(mx, m0, m1);
-      mx = fmaxf(m0, m1);
-      float l = 0.f;
-#pragma unroll
-      for (int e = 0; e < 12; ++e) { sT[e] = expf(sT[e] - mx); l += sT[e]; }
-#pragma unroll
-      for (int e = 12; e < 16; ++e) sT[e] = 0.f;            // keys 24 .. 31 do not exist
-      float l0, l1;
-      tf_halves(l, l0, l1);
-      const float il = 1.0f / (l0 + l1);
-#pragma unroll
-      for (int e = 0; e < 12; ++e) sT[e] *= il;
-    }
+    tf_softmax24(sT, Bs[h], tok ? li : TF_NT - 1, hh);      // (columns of nonexistent queries are never stored)
     // ---- O^T = V^T P^T
     __builtin_amdgcn_wave_barrier();
     float va[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) va[m] = vt[tf_key(m, hh) * TF_VST + li];
-    f32x16 oT;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oT[e] = 0.f;
+    f32x16 oT = tf_zero();
 #pragma unroll
     for (int m = 0; m < 16; ++m) oT = __builtin_amdgcn_mfma_f32_32x32x2f32(va[m], sT[m], oT, 0, 0, 0);
     __syncthreads();                                                                  // S2: max|v| of the four heads; planes A free
@@ -259,9 +179,7 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
     float* yb = p.y + row0 * C;
 #pragma unroll 1
     for (int mt = 0; mt < MT; ++mt) {
-      f32x16 y;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) y[e] = 0.f;
+      f32x16 y = tf_zero();
       half8 u0h[2], u0l[2], u1h[2], u1l[2];                 // two fragment sets, as in the projection
       auto uload = [&](half8 (&uh)[2], half8 (&ul)[2], int t) {
         const unsigned o = (unsigned)(mt * 4 + t) * 2048u;
@@ -273,9 +191,7 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
         for (int s = 0; s < 2; ++s) {
           const half8 oh = *reinterpret_cast<const half8*>(Oh + rb * TW_OST + 32 * t + 16 * hh + 8 * s);
           const half8 ol = *reinterpret_cast<const half8*>(Ol + rb * TW_OST + 32 * t + 16 * hh + 8 * s);
-          y = __builtin_amdgcn_mfma_f32_32x32x16_f16(uh[s], ol, y, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_32x32x16_f16(ul[s], oh, y, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_32x32x16_f16(uh[s], oh, y, 0, 0, 0);
+          y = tf_mfma3(uh[s], ul[s], oh, ol, y);
         }
       };
 #pragma unroll 1
@@ -312,20 +228,9 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
   }
 }
 
-static int tw_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
 // C = 128 / 256, 24 frames, forward only (attn_fused.hip routes here; qkv_out / rec_v are not produced)
 int wdno_tattn_fused_fwd_wide_launch(const TFusedP& p, int C, hipStream_t st) {
-  int64_t grid = 2 * (int64_t)tw_num_cus();
+  int64_t grid = 2 * (int64_t)wdno_num_cus();
   if (grid > p.nseq) grid = p.nseq;
   if (C == 128) tattn_wide_fwd_kernel<128><<<(int)grid, 256, 0, st>>>(p);
   else if (C == 256) tattn_wide_fwd_kernel<256><<<(int)grid, 256, 0, st>>>(p);

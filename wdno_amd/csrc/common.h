@@ -22,6 +22,9 @@ static inline int wdno_check_launch() {
 
 static inline hipStream_t as_stream(wdno_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// compute units of the current device (api.cpp): cached after the first successful query, 256 when the query fails or reports 0
+int wdno_num_cus();
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 

@@ -618,10 +618,7 @@ extern "C" size_t wdno_conv_fwd_split_ws_bytes(const wdno_conv_geom* g) {
   ConvP p;
   fill_params(p, g);
   if (!p.identity_out || !wdno_conv_h3t_takes(*g)) return 0;
-  int dev = 0, cus = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-  const int runs = wdno_conv_h3t_split(*g, p.P, cus & ~7);
+  const int runs = wdno_conv_h3t_split(*g, p.P, wdno_num_cus() & ~7);
   return runs > 1 ? (size_t)runs * p.P * g->K * sizeof(float) : 0;
 }
 extern "C" int wdno_conv_fwd_bf16(const void* x16, const void* wp16, const float* bias, const float* residual, float* y, float* amax_rec,

@@ -336,17 +336,6 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * (WM * WN) + wave);
 }
 
-static int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
 template <int BM, int BN, int WM, int WN, int NS, bool LP>
 static int launch_h3d(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
                       const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
@@ -360,7 +349,7 @@ static int launch_h3d(const void* xh, const void* xl, const void* wh, const void
   const int64_t x_elems = (int64_t)g.N * g.D * g.H * g.W * g.C;
   const int64_t w_elems = (int64_t)g.kd * g.kh * g.K * p.R;
   if (x_elems * 2 >= DMA_OOB || w_elems * 2 >= DMA_OOB || p.P >= 0x7fffffff) return WDNO_EUNSUPPORTED;
-  int grid = num_cus() & ~7;                      // one persistent block per CU (the LDS ring allows no more), multiple of the 8 XCDs
+  int grid = wdno_num_cus() & ~7;                      // one persistent block per CU (the LDS ring allows no more), multiple of the 8 XCDs
   if (grid < 8) grid = 8;
   if (p.ntiles < grid) grid = p.ntiles;
   const bool uni = (g.C % 32) == 0;
@@ -389,7 +378,7 @@ static int fwd_h3_dma(const void* xh, const void* xl, const void* wh, const void
   // traffic a shape needs per MFMA. Examples on 256 CUs: a 256-channel layer at the 10 x 10 level is 300 tiles of 128 x 128 --
   // two rounds, the second with 44 tiles -- but 200 tiles of 192 x 128 (0.258 -> 0.196 ms); a 64-channel layer at the 20 x 20
   // level is 300 tiles of 256 x 64 but 400 shorter ones of 192 x 64 (0.329 -> 0.267 ms).
-  const int cus = num_cus() & ~7;
+  const int cus = wdno_num_cus() & ~7;
   auto cost = [&](int bm, int bn, double weight) {
     return (double)(cdiv64(cdiv64(p.P, bm) * cdiv(g.K, bn), cus) * bm * bn) * weight;
   };

@@ -552,17 +552,6 @@ __global__ __launch_bounds__(256) void conv_split_reduce_kernel(const float4* __
   if (amax_rec) wave_amax_emit(am, amax_rec, (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
 }
 
-static int t_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
 template <int BM, int BN, int WM, int WN, int KW, int CB, bool LP, bool SP = false>
 static int launch_h3t(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
                       const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
@@ -583,7 +572,7 @@ static int launch_h3t(const void* xh, const void* xl, const void* wh, const void
     if (p.tsplit < 2 || ((CB / 16) * KW & 1) || nst % p.tsplit || !p.split_ws || (size_t)p.tsplit * p.P * g.K * sizeof(float) > p.split_ws_bytes || (g.K & 3))
       return WDNO_EINVAL;
   } else p.tsplit = 1;
-  int grid = t_num_cus() & ~7;
+  int grid = wdno_num_cus() & ~7;
   if (grid < 8) grid = 8;
   if ((int64_t)p.ntiles * p.tsplit < grid) grid = p.ntiles * p.tsplit;
   static bool done = false;
@@ -640,13 +629,13 @@ int wdno_conv_fwd_h3_tap(int shape, const void* xh, const void* xl, const void* 
     if (p.zb_blocks >= ncb) p.zb_blocks = ncb - 1;          // (a tile must keep at least its centre stage: t_live_stages)
     // less than one round of 256-pixel tiles (the stem at batch 1: 150 tiles on 256 CUs): 192-pixel tiles fill the chip and end a quarter
     // earlier (128-pixel tiles would need a second round) -- WDNO_DBG_STEM_TILES_256: the 256-pixel tiles always
-    const int cus = t_num_cus();
+    const int cus = wdno_num_cus();
     if (xl != nullptr && cdiv64(p.P, 256) < cus && cdiv64(p.P, 192) <= cus && cdiv64(p.P, 192) > cdiv64(p.P, 256) && wdno_debug_mode != WDNO_DBG_STEM_TILES_256)
       return launch_h3t<192, 64, 2, 2, 7, 16, false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
     if (xl == nullptr) return launch_h3t<256, 64, 4, 1, 7, 16, true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
     return launch_h3t<256, 64, 4, 1, 7, 16, false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
   }
-  if (xl == nullptr && p.g.K > 64 && cdiv64(p.P, 256) * cdiv(p.g.K, 128) >= 2 * t_num_cus())
+  if (xl == nullptr && p.g.K > 64 && cdiv64(p.P, 256) * cdiv(p.g.K, 128) >= 2 * wdno_num_cus())
     return launch_h3t<256, 128, 4, 1, 3, 32, true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
   if (xl == nullptr) return fwd_h3t<true>(shape, xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
   return fwd_h3t<false>(shape, xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);

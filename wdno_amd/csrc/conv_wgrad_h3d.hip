@@ -1032,17 +1032,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3s_kernel(const _Float16* __r
   else run(std::integral_constant<int, 2>{});
 }
 
-static int wd_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
 // geometries of the window kernel: stride 1, equal grids, kw == 3, whole 64-channel tiles (WDNO_DBG_CHUNKED_DMA_CONV: never; WDNO_DBG_PER_AXIS_DWT_AND_WGRAD_WINDOW_K64: only for
 // K <= 64 -- with more output channels the windows are fetched once per 64-wide k tile)
 static bool wd_window_takes(const wdno_conv_geom* g) {
@@ -1088,7 +1077,7 @@ void wdno_wgrad_h3d_plan(const wdno_conv_geom* g, int* bm, int* bn, int* splits,
     // empty window: tkc * (ntap / 2) * S + tkc * ceil(S / 2) items of equal length for S splits. Taken when one round of the CUs still holds
     // them (a block then sees items of one kind only) and the items get SHORTER than in the plan above (WDNO_DBG_WGRAD_NO_SPLIT_PAIR: never -- the A/B).
     if (splitpair && (ntap & 1) && wdno_debug_mode != WDNO_DBG_WGRAD_NO_SPLIT_PAIR) {
-      const int blocks = wd_num_cus() >= 256 ? 256 : (wd_num_cus() & ~7);      // what launch_ww starts at most (it walks items <= blocks one per block)
+      const int blocks = wdno_num_cus() >= 256 ? 256 : (wdno_num_cus() & ~7);      // what launch_ww starts at most (it walks items <= blocks one per block)
       int64_t S = max_splits < 256 ? max_splits : 256;
       while (S >= 2 && (int64_t)tkc * (ntap / 2) * S + (int64_t)tkc * ((S + 1) / 2) > blocks) --S;
       if (S >= 2) {
@@ -1123,13 +1112,13 @@ static void launch_wd(const void* xh, const void* xl, const void* dyh, const voi
   const size_t lds = (size_t)NS * (LP ? 1 : 2) * (32 * (BM / 8) * 16 + 32 * (BN / 8) * 16);
   static bool done = false;
   if (!done) { (void)hipFuncSetAttribute((const void*)conv_wgrad_h3d_kernel<BM, BN, NS, LP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
-  int grid = wd_num_cus();
+  int grid = wdno_num_cus();
   if (w.items < grid) grid = w.items;
   WgradDP wl = w;
   wl.xcd_chunk = 0;
   if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {          // WDNO_DBG_WGRAD_NO_XCD_GROUPING: round-robin items (the A/B for the XCD grouping)
     wl.xcd_chunk = cdiv(w.items, 8);
-    grid = wd_num_cus() & ~7;
+    grid = wdno_num_cus() & ~7;
     if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;      // every XCD's blocks walk its chunk in whole rounds; spare blocks idle
   }
   conv_wgrad_h3d_kernel<BM, BN, NS, LP><<<grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)dyh, (const _Float16*)dyl,
@@ -1147,13 +1136,13 @@ static void launch_ww(const void* xh, const void* xl, const void* dyh, const voi
   const size_t lds = (size_t)NS * (LP ? 1 : 2) * (2 * 4096 + 2 * 5120);      // two dy tiles + two windows per plane set and stage
   static bool done = false;
   if (!done) { (void)hipFuncSetAttribute((const void*)conv_wgrad_h3w_kernel<NS, LP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
-  int grid = wd_num_cus();
+  int grid = wdno_num_cus();
   if (w.items < grid) grid = w.items;
   WgradDP wl = w;
   wl.xcd_chunk = 0;
   if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {
     wl.xcd_chunk = cdiv(w.items, 8);
-    grid = wd_num_cus() & ~7;
+    grid = wdno_num_cus() & ~7;
     if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;
   }
   conv_wgrad_h3w_kernel<NS, LP><<<grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)dyh, (const _Float16*)dyl,
@@ -1167,13 +1156,13 @@ static void launch_ws(const void* xh, const void* xl, const void* dyh, const voi
   const unsigned x_bytes = (unsigned)((int64_t)g.N * g.D * g.H * g.W * g.C * 2);
   const unsigned dy_bytes = (unsigned)((int64_t)g.N * g.YD * g.YH * g.YW * g.K * 2);
   const size_t lds = (size_t)WDNO_H3S_STAGES * (LP ? 1 : 2) * (4096 + 4096);
-  int grid = wd_num_cus();
+  int grid = wdno_num_cus();
   if (w.items < grid) grid = w.items;
   WgradDP wl = w;
   wl.xcd_chunk = 0;
   if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {
     wl.xcd_chunk = cdiv(w.items, 8);
-    grid = wd_num_cus() & ~7;
+    grid = wdno_num_cus() & ~7;
     if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;
   }
   conv_wgrad_h3s_kernel<LP><<<grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)dyh, (const _Float16*)dyl,

@@ -1,4 +1,6 @@
-// linattn_fused.h -- shared by the fused SpatialLinearAttention forward kernels (linattn_fused.hip: 64 channels; linattn_fused_wide.hip: 128 / 256).
+// linattn_fused.h -- what only the fused SpatialLinearAttention kernels share: the launch parameters of the forward passes (linattn_fused.hip: 64
+// channels; linattn_fused_wide.hip: 128 / 256) and the cut of a frame into token chunks (forward and linattn_fused_bwd.hip). The lane-level steps are
+// in attn_fused.h.
 #pragma once
 #include "attn_fused.h"
 
@@ -15,14 +17,13 @@ struct LFusedP {
   int n_tok, chunks, tiles_per_chunk; float scale;
 };
 
-__device__ __forceinline__ f32x16 lf_zero() {
-  f32x16 z;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) z[e] = 0.f;
-  return z;
-}
-__device__ __forceinline__ f32x16 lf_mfma3(half8 ah, half8 al, half8 bh, half8 bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
+// token chunks per frame: ~3 blocks per CU in flight, at least two tiles each. The layout of the forward's workspace and of the backward's
+// first pass (one partial per chunk) both follow from it.
+static inline int lf_chunks(int64_t units, int n_tok) {
+  const int ntiles = (n_tok + 31) / 32;
+  int64_t c = (3 * (int64_t)wdno_num_cus() + units - 1) / units;
+  if (c > ntiles / 2) c = ntiles / 2;
+  if (c < 1) c = 1;
+  if (c > 64) c = 64;
+  return (int)c;
 }

@@ -15,25 +15,9 @@
 //   lattn_fused_out_kernel   q of a tile in the usual [feature][token] layout (softmax over d inside a lane pair), out^T = ctx^T qs^T on
 //                            the exact-fp32 MFMA with qs in place, to_out on the split MFMA straight from the accumulators, heads summed
 //                            through LDS with the bias and the residual (as attn_fused.hip).
+// LayerNorm row, split MFMA, softmax over the features, W_out fragments and the partial-tile store are the tf_ functions of attn_fused.h;
+// linattn_fused.h has the launch parameters and lf_chunks, which the backward shares.
 #include "linattn_fused.h"
-
-// LayerNorm of one row by its 16 lanes (norm.hip: layernorm_kernel) -> (hi, lo) planes
-__device__ __forceinline__ void lf_ln_row(float4 xv, float4 g, float eps, float ps, _Float16* __restrict__ Ah, _Float16* __restrict__ Al, int row, int c4) {
-  const float mean = tf_row16_sum((xv.x + xv.y) + (xv.z + xv.w)) * (1.0f / TF_C);
-  xv.x -= mean; xv.y -= mean; xv.z -= mean; xv.w -= mean;
-  const float var = tf_row16_sum((xv.x * xv.x + xv.y * xv.y) + (xv.z * xv.z + xv.w * xv.w)) * (1.0f / TF_C);
-  const float rstd = 1.0f / sqrtf(var + eps);
-  const float o[4] = {xv.x * rstd * g.x, xv.y * rstd * g.y, xv.z * rstd * g.z, xv.w * rstd * g.w};
-  half4v h, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float t = o[j] * ps;
-    h[j] = (_Float16)t;
-    l[j] = (_Float16)(t - (float)h[j]);
-  }
-  *reinterpret_cast<half4v*>(Ah + row * TF_AST + 4 * c4) = h;
-  *reinterpret_cast<half4v*>(Al + row * TF_AST + 4 * c4) = l;
-}
 
 // ------------------------------------------------------------------------------------------------ pass 1: per-chunk context
 __global__ __launch_bounds__(256, 2) void lattn_fused_ctx_kernel(LFusedP p) {
@@ -62,7 +46,7 @@ __global__ __launch_bounds__(256, 2) void lattn_fused_ctx_kernel(LFusedP p) {
   const int tile1 = min(ntiles, tile0 + p.tiles_per_chunk);
 
   float m_run = -INFINITY, z_run = 0.f;                 // feature d = li: running maximum over the tokens so far (same in both lane halves), partial sum of this half
-  f32x16 ctx = lf_zero();                               // ctx_raw[d][e]: lane (e, hh), register r <-> d = tf_key(r, hh)
+  f32x16 ctx = tf_zero();                               // ctx_raw[d][e]: lane (e, hh), register r <-> d = tf_key(r, hh)
   float4 nx0 = make_float4(0.f, 0.f, 0.f, 0.f), nx1 = nx0;
   auto fetch = [&](int tile) {
     const int r0 = tile * 32 + lrow, r1 = r0 + 16;
@@ -71,18 +55,18 @@ __global__ __launch_bounds__(256, 2) void lattn_fused_ctx_kernel(LFusedP p) {
   };
   if (tile0 < tile1) fetch(tile0);
   for (int tile = tile0; tile < tile1; ++tile) {
-    lf_ln_row(nx0, g4, p.eps, ps, Ah, Al, lrow, lc4);
-    lf_ln_row(nx1, g4, p.eps, ps, Ah, Al, 16 + lrow, lc4);
+    tf_ln_row(nx0, g4, p.eps, ps, Ah, Al, lrow, lc4);
+    tf_ln_row(nx1, g4, p.eps, ps, Ah, Al, 16 + lrow, lc4);
     __syncthreads();
     if (tile + 1 < tile1) fetch(tile + 1);
     // k[tok][d], v[tok][e] of the tile: rows = tokens (A = the token planes), columns = features (B = the weight rows)
-    f32x16 ak = lf_zero(), av = lf_zero();
+    f32x16 ak = tf_zero(), av = tf_zero();
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const half8 ah = *reinterpret_cast<const half8*>(Ah + li * TF_AST + 16 * s + 8 * hh);
       const half8 al = *reinterpret_cast<const half8*>(Al + li * TF_AST + 16 * s + 8 * hh);
-      ak = lf_mfma3(ah, al, wkh[s], wkl[s], ak);
-      av = lf_mfma3(ah, al, wvh[s], wvl[s], av);
+      ak = tf_mfma3(ah, al, wkh[s], wkl[s], ak);
+      av = tf_mfma3(ah, al, wvh[s], wvl[s], av);
     }
     __syncthreads();                                     // the planes may be rewritten
     const int tok0 = tile * 32;
@@ -177,13 +161,7 @@ __global__ __launch_bounds__(256, 2) void lattn_fused_out_kernel(LFusedP p) {
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int off = (32 * ct + li) * TF_HD + 32 * h + 16 * s + 4 * hh;
-      const half4v a = *reinterpret_cast<const half4v*>(p.wo_hi + off), b = *reinterpret_cast<const half4v*>(p.wo_hi + off + 8);
-      const half4v c = *reinterpret_cast<const half4v*>(p.wo_lo + off), d = *reinterpret_cast<const half4v*>(p.wo_lo + off + 8);
-      woh[ct][s] = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-      wol[ct][s] = __builtin_shufflevector(c, d, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
+    for (int s = 0; s < 2; ++s) tf_wout_frag(p.wo_hi, p.wo_lo, ct, h, s, li, hh, woh[ct][s], wol[ct][s]);
   // ctx^T fragments of this (frame, head): step r contracts the features d = tf_key(r, hh); lane li = output feature e
   float ctxf[16];
   float amc = 0.f;
@@ -213,62 +191,36 @@ __global__ __launch_bounds__(256, 2) void lattn_fused_out_kernel(LFusedP p) {
   if (tile0 < tile1) fetch(tile0);
   for (int tile = tile0; tile < tile1; ++tile) {
     const float4 x0 = nx0, x1 = nx1;                     // the residual rows of this tile
-    lf_ln_row(x0, g4, p.eps, ps, Ah, Al, lrow, lc4);
-    lf_ln_row(x1, g4, p.eps, ps, Ah, Al, 16 + lrow, lc4);
+    tf_ln_row(x0, g4, p.eps, ps, Ah, Al, lrow, lc4);
+    tf_ln_row(x1, g4, p.eps, ps, Ah, Al, 16 + lrow, lc4);
     __syncthreads();
     if (tile + 1 < tile1) fetch(tile + 1);
     // q^T of the head: [feature][token], a lane owns one token and the features 8 c + 4 hh + (0..3)
-    f32x16 aq = lf_zero();
+    f32x16 aq = tf_zero();
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const half8 bh = *reinterpret_cast<const half8*>(Ah + li * TF_AST + 16 * s + 8 * hh);
       const half8 bl = *reinterpret_cast<const half8*>(Al + li * TF_AST + 16 * s + 8 * hh);
-      aq = lf_mfma3(wqh[s], wql[s], bh, bl, aq);
+      aq = tf_mfma3(wqh[s], wql[s], bh, bl, aq);
     }
     // qs = scale softmax over the head's 32 features of the token (16 here, 16 in lane ^ 32)
-    {
-      float mx = -INFINITY;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) { aq[e] *= inv_qkv; mx = fmaxf(mx, aq[e]); }
-      float m0, m1;
-      tf_halves(mx, m0, m1);
-      mx = fmaxf(m0, m1);
-      float l = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { aq[e] = expf(aq[e] - mx); l += aq[e]; }
-      float l0, l1;
-      tf_halves(l, l0, l1);
-      const float il = p.scale / (l0 + l1);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) aq[e] *= il;
-    }
+    for (int e = 0; e < 16; ++e) aq[e] *= inv_qkv;
+    tf_softmax_d(aq, p.scale);
     // out^T[e][tok] = sum_d ctx[d][e] qs[tok][d] (exact fp32, qs in place)
-    f32x16 oT = lf_zero();
+    f32x16 oT = tf_zero();
 #pragma unroll
     for (int r = 0; r < 16; ++r) oT = __builtin_amdgcn_mfma_f32_32x32x2f32(ctxf[r], aq[r], oT, 0, 0, 0);
     // to_out, this head's 32 of the 128 reduction values: y_part[c][token]
     half8 oh[2], ol[2];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const float t = oT[e] * so;
-      const _Float16 th = (_Float16)t;
-      oh[e >> 3][e & 7] = th;
-      ol[e >> 3][e & 7] = (_Float16)(t - (float)th);
-    }
-    f32x16 y0 = lf_zero(), y1 = lf_zero();
+    tf_split16(oT, so, oh, ol);
+    f32x16 y0 = tf_zero(), y1 = tf_zero();
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      y0 = lf_mfma3(woh[0][s], wol[0][s], oh[s], ol[s], y0);
-      y1 = lf_mfma3(woh[1][s], wol[1][s], oh[s], ol[s], y1);
+      y0 = tf_mfma3(woh[0][s], wol[0][s], oh[s], ol[s], y0);
+      y1 = tf_mfma3(woh[1][s], wol[1][s], oh[s], ol[s], y1);
     }
-    {
-      float* yp = Yp[h] + li * TF_YST + 4 * hh;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        *reinterpret_cast<float4*>(yp + 8 * c) = make_float4(y0[4 * c] * inv_o, y0[4 * c + 1] * inv_o, y0[4 * c + 2] * inv_o, y0[4 * c + 3] * inv_o);
-        *reinterpret_cast<float4*>(yp + 32 + 8 * c) = make_float4(y1[4 * c] * inv_o, y1[4 * c + 1] * inv_o, y1[4 * c + 2] * inv_o, y1[4 * c + 3] * inv_o);
-      }
-    }
+    tf_partial_store(Yp[h] + li * TF_YST + 4 * hh, y0, y1, inv_o);
     __syncthreads();
     // heads summed, bias and residual added, rows stored (the lanes that loaded a row finish it)
     auto finish = [&](int row, const float4& xr) {
@@ -288,26 +240,6 @@ __global__ __launch_bounds__(256, 2) void lattn_fused_out_kernel(LFusedP p) {
     // (the next tile's planes are written before its barrier, the partial tiles after it: no third barrier)
   }
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * TF_HEADS + h);
-}
-
-static int lf_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-// token chunks per frame: ~3 blocks per CU in flight, at least two tiles each
-static int lf_chunks(int64_t units, int n_tok) {
-  const int ntiles = (n_tok + 31) / 32;
-  int64_t c = (3 * (int64_t)lf_num_cus() + units - 1) / units;
-  if (c > ntiles / 2) c = ntiles / 2;
-  if (c < 1) c = 1;
-  if (c > 64) c = 64;
-  return (int)c;
 }
 
 // 128 / 256 channels: linattn_fused_wide.hip (forward only; operands of pack modes 10 / 11)

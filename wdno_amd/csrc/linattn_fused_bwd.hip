@@ -18,9 +18,11 @@
 //                              power-of-two scales, MFMA accumulators over all tiles of the block, in-place MFMA rescale), dxn = W^T dqkv^T from the
 //                              swizzled LDS image of W_qkv, LayerNorm backward, residual gradient. One partial [dW_qkv | dW_out | dgamma | db_out] per
 //                              block, summed in block order by lattn_fused_reduce_kernel: no atomics, bit-reproducible.
-#include "attn_fused.h"
+// The helpers this kernel has in common with attn_fused_bwd.hip (transpose reads of the swizzled W image, (hi, lo) splits, running scales, LayerNorm
+// row with mean / 1/std) are the tf_ functions of attn_fused.h; the cut into chunks of pass 1 is linattn_fused.h's lf_chunks, the same function that
+// lays out the forward's workspace. lb_ / LB_ names are what only this file has (32-row images: lb_trf; table products: lb_product16; lb_chunks2).
+#include "linattn_fused.h"
 
-#define LB_PS 36                      /* halves per row of a per-head plane tile */
 #define LB_N_WQ (3 * TF_HD * TF_C)
 #define LB_N_WO (TF_C * TF_HD)
 #define LB_OFF_WO LB_N_WQ
@@ -55,133 +57,18 @@ struct LBwdP {
   int chunks2, tiles_per_chunk2;          // pass 2 (persistent grid): its own cut of the frames, chosen for equal tiles per block
 };
 
-typedef short lb_short4 __attribute__((ext_vector_type(4)));
-typedef short lb_short8 __attribute__((ext_vector_type(8)));
-typedef lb_short4 __attribute__((address_space(3))) * lb_lds_s4;
-
-__device__ __forceinline__ half8 lb_tr2(const _Float16* p0, const _Float16* p1) {
-  const lb_short4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lb_lds_s4)(p0));
-  const lb_short4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lb_lds_s4)(p1));
-  const lb_short8 c = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(half8, c);
-}
 // operand fragment from a [token][channel] image of 32 rows: lane (li, hh) receives channel ch0 + li of tokens tok0 + 8 hh + (0..7)
 __device__ __forceinline__ half8 lb_trf(const _Float16* tile, int stride, int tok0, int ch0, int lane) {
   const int g = lane >> 4, xl = lane & 15;
   const _Float16* p0 = tile + (tok0 + 8 * (g >> 1) + (xl >> 2)) * stride + ch0 + 16 * (g & 1) + 4 * (xl & 3);
-  return lb_tr2(p0, p0 + 4 * stride);
-}
-__device__ __forceinline__ int lb_woff(int f, int chunk) { return f * TF_C + ((chunk ^ ((f >> 1) & 7)) << 3); }
-// W^T fragment for dxn^T[c][tok] = sum_f W[f][c] d[tok][f] (attn_fused_bwd.hip: tb_wtr)
-__device__ __forceinline__ half8 lb_wtr(const _Float16* W, int f0, int ct, int lane) {
-  const int g = lane >> 4, xl = lane & 15;
-  const int ra = f0 + 4 * (g >> 1) + (xl >> 2), rb = ra + 8;
-  const int col = 32 * ct + 16 * (g & 1) + 4 * (xl & 3);
-  return lb_tr2(W + lb_woff(ra, col >> 3) + (col & 7), W + lb_woff(rb, col >> 3) + (col & 7));
-}
-__device__ __forceinline__ f32x16 lb_zero() {
-  f32x16 z;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) z[e] = 0.f;
-  return z;
-}
-__device__ __forceinline__ f32x16 lb_mfma3(half8 ah, half8 al, half8 bh, half8 bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
+  return tf_tr2(p0, p0 + 4 * stride);
 }
 // D^T[i][tok] = sum over the 32 features of a 32 x 32 table fragment (lane = i) and an accumulator tile in place
 __device__ __forceinline__ f32x16 lb_product16(const float (&a)[16], const f32x16& b) {
-  f32x16 acc = lb_zero();
+  f32x16 acc = tf_zero();
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[r], b[r], acc, 0, 0, 0);
   return acc;
-}
-__device__ __forceinline__ void lb_split16(const f32x16& v, float s, half8 (&h)[2], half8 (&l)[2], _Float16* __restrict__ Ph, _Float16* __restrict__ Pl,
-                                           int li, int hh) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const float t = v[e] * s;
-    const _Float16 th = (_Float16)t;
-    h[e >> 3][e & 7] = th;
-    l[e >> 3][e & 7] = (_Float16)(t - (float)th);
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    half4v a, b;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { a[j] = h[c >> 1][4 * (c & 1) + j]; b[j] = l[c >> 1][4 * (c & 1) + j]; }
-    *reinterpret_cast<half4v*>(Ph + li * LB_PS + 8 * c + 4 * hh) = a;
-    *reinterpret_cast<half4v*>(Pl + li * LB_PS + 8 * c + 4 * hh) = b;
-  }
-}
-__device__ __forceinline__ void lb_ln_row(float4 xv, float4 g, float eps, float ps, _Float16* __restrict__ Ah, _Float16* __restrict__ Al, int row, int c4,
-                                          float& mean, float& rstd) {
-  mean = tf_row16_sum((xv.x + xv.y) + (xv.z + xv.w)) * (1.0f / TF_C);
-  xv.x -= mean; xv.y -= mean; xv.z -= mean; xv.w -= mean;
-  const float var = tf_row16_sum((xv.x * xv.x + xv.y * xv.y) + (xv.z * xv.z + xv.w * xv.w)) * (1.0f / TF_C);
-  rstd = 1.0f / sqrtf(var + eps);
-  const float o[4] = {xv.x * rstd * g.x, xv.y * rstd * g.y, xv.z * rstd * g.z, xv.w * rstd * g.w};
-  half4v h, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float t = o[j] * ps;
-    h[j] = (_Float16)t;
-    l[j] = (_Float16)(t - (float)h[j]);
-  }
-  *reinterpret_cast<half4v*>(Ah + row * TF_AST + 4 * c4) = h;
-  *reinterpret_cast<half4v*>(Al + row * TF_AST + 4 * c4) = l;
-}
-__device__ __forceinline__ void lb_plane_row(float4 v, float s, _Float16* __restrict__ Ah, _Float16* __restrict__ Al, int row, int c4) {
-  const float o[4] = {v.x, v.y, v.z, v.w};
-  half4v h, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float t = o[j] * s;
-    h[j] = (_Float16)t;
-    l[j] = (_Float16)(t - (float)h[j]);
-  }
-  *reinterpret_cast<half4v*>(Ah + row * TF_AST + 4 * c4) = h;
-  *reinterpret_cast<half4v*>(Al + row * TF_AST + 4 * c4) = l;
-}
-__device__ __forceinline__ float lb_scale(float bound) { return fminf(fmaxf(scale_from_amax(bound), 0x1p-100f), 0x1p100f); }
-// w *= r in place on the matrix pipe (attn_fused_bwd.hip: tb_rescale)
-__device__ __forceinline__ void lb_rescale(f32x16& w, float r, int li, int hh) {
-  const float r1 = r - 1.0f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) w = __builtin_amdgcn_mfma_f32_32x32x2f32(li == tf_key(e, hh) ? r1 : 0.f, w[e], w, 0, 0, 0);
-}
-__device__ __forceinline__ void lb_fit(float& sc, float amax, f32x16& w0, f32x16& w1, int li, int hh) {
-  const float need = lb_scale(amax);
-  if (need < sc) {
-    const float r = need / sc;
-    lb_rescale(w0, r, li, hh);
-    lb_rescale(w1, r, li, hh);
-    sc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(need)));
-  }
-}
-__device__ __forceinline__ float lb_absmax16(const f32x16& v) {
-  float m = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) m = fmaxf(m, fabsf(v[e]));
-  return m;
-}
-// qs = scale softmax over the head's 32 features of the token (16 in this lane, 16 in lane ^ 32), in place
-__device__ __forceinline__ void lb_softmax_d(f32x16& aq, float scale) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) mx = fmaxf(mx, aq[e]);
-  float m0, m1;
-  tf_halves(mx, m0, m1);
-  mx = fmaxf(m0, m1);
-  float l = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) { aq[e] = expf(aq[e] - mx); l += aq[e]; }
-  float l0, l1;
-  tf_halves(l, l0, l1);
-  const float il = scale / (l0 + l1);
-#pragma unroll
-  for (int e = 0; e < 16; ++e) aq[e] *= il;
 }
 
 // ------------------------------------------------------------------------------------------------ pass 1: dctx per chunk
@@ -206,13 +93,13 @@ __global__ __launch_bounds__(256, 2) void lattn_fused_dctx_kernel(LBwdP p) {
   const float4 g4 = reinterpret_cast<const float4*>(p.gamma)[lc4];
   const float ps = scale_from_amax(8.0f * group_max<16>(amax4(0.f, g4)));
   const float inv_qkv = 1.0f / (ps * p.wq_scale[0]);
-  const float sc_g = lb_scale(amax_record_read(p.rec_dy));
+  const float sc_g = tf_scale(amax_record_read(p.rec_dy));
   const float* xu = p.x + (int64_t)unit * p.n_tok * TF_C;
   const float* gu = p.dy + (int64_t)unit * p.n_tok * TF_C;
   const int tile0 = chunk * p.tiles_per_chunk;
   const int ntiles = (p.n_tok + 31) >> 5;
   const int tile1 = min(ntiles, tile0 + p.tiles_per_chunk);
-  f32x16 acc = lb_zero();                               // dctx[d][e] of this chunk: lane (e, hh), register r <-> d = tf_key(r, hh)
+  f32x16 acc = tf_zero();                               // dctx[d][e] of this chunk: lane (e, hh), register r <-> d = tf_key(r, hh)
   float4 nx0 = make_float4(0.f, 0.f, 0.f, 0.f), nx1 = nx0, ng0 = nx0, ng1 = nx0;
   auto fetch = [&](int tile) {
     const int r0 = tile * 32 + lrow, r1 = r0 + 16;
@@ -225,26 +112,26 @@ __global__ __launch_bounds__(256, 2) void lattn_fused_dctx_kernel(LBwdP p) {
   if (tile0 < tile1) fetch(tile0);
   for (int tile = tile0; tile < tile1; ++tile) {
     float mean, rstd;
-    lb_ln_row(nx0, g4, p.eps, ps, Ah, Al, lrow, lc4, mean, rstd);
-    lb_ln_row(nx1, g4, p.eps, ps, Ah, Al, 16 + lrow, lc4, mean, rstd);
-    lb_plane_row(ng0, sc_g, Gh, Gl, lrow, lc4);
-    lb_plane_row(ng1, sc_g, Gh, Gl, 16 + lrow, lc4);
+    tf_ln_row(nx0, g4, p.eps, ps, Ah, Al, lrow, lc4, mean, rstd);
+    tf_ln_row(nx1, g4, p.eps, ps, Ah, Al, 16 + lrow, lc4, mean, rstd);
+    tf_plane_row(ng0, sc_g, Gh, Gl, lrow, lc4);
+    tf_plane_row(ng1, sc_g, Gh, Gl, 16 + lrow, lc4);
     __syncthreads();
     if (tile + 1 < tile1) fetch(tile + 1);
-    f32x16 aq = lb_zero(), dT = lb_zero();
+    f32x16 aq = tf_zero(), dT = tf_zero();
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const half8 xh = *reinterpret_cast<const half8*>(Ah + li * TF_AST + 16 * s + 8 * hh);
       const half8 xl = *reinterpret_cast<const half8*>(Al + li * TF_AST + 16 * s + 8 * hh);
       const half8 gh = *reinterpret_cast<const half8*>(Gh + li * TF_AST + 16 * s + 8 * hh);
       const half8 gl = *reinterpret_cast<const half8*>(Gl + li * TF_AST + 16 * s + 8 * hh);
-      aq = lb_mfma3(wqh[s], wql[s], xh, xl, aq);                 // q^T[d][tok]: a lane owns a token
-      dT = lb_mfma3(gh, gl, woth[s], wotl[s], dT);               // dout[tok][e] (swapped operands): a lane owns the feature e, 16 tokens
+      aq = tf_mfma3(wqh[s], wql[s], xh, xl, aq);                 // q^T[d][tok]: a lane owns a token
+      dT = tf_mfma3(gh, gl, woth[s], wotl[s], dT);               // dout[tok][e] (swapped operands): a lane owns the feature e, 16 tokens
     }
     __syncthreads();                                             // the planes may be rewritten
 #pragma unroll
     for (int e = 0; e < 16; ++e) aq[e] *= inv_qkv;
-    lb_softmax_d(aq, p.scale);
+    tf_softmax_d(aq, p.scale);
     // qs -> [token][feature] through the head's tile: a lane then owns the feature d and the tokens tf_key(m, hh)
     float* tq = Tq[h];
 #pragma unroll
@@ -302,14 +189,14 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
   const int lrow = tid >> 4, lc4 = tid & 15;
   float* Yp = reinterpret_cast<float*>(lb_smem + LB_L_Y + h * LB_HEAD_LDS);
   _Float16* PH = reinterpret_cast<_Float16*>(Yp);
-  _Float16* PL = PH + 32 * LB_PS;
+  _Float16* PL = PH + 32 * TF_PS;
   float* KM = reinterpret_cast<float*>(lb_smem + LB_L_TAB) + h * 96;
   float* KZ = KM + 32;
   float* KT = KM + 64;
 
   for (int q = tid; q < 3 * TF_HD * 8; q += 256) {                // W_qkv planes -> LDS (swizzled: attn_fused_bwd.hip)
     const int f = q >> 3, ch = q & 7;
-    const int dst = lb_woff(f, ch);
+    const int dst = tf_woff(f, ch);
     *reinterpret_cast<uint4*>(WH + dst) = *reinterpret_cast<const uint4*>(p.wq_hi + f * TF_C + ch * 8);
     *reinterpret_cast<uint4*>(WL + dst) = *reinterpret_cast<const uint4*>(p.wq_lo + f * TF_C + ch * 8);
   }
@@ -319,15 +206,15 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
   const float ps = scale_from_amax(8.0f * group_max<16>(amax4(0.f, g4)));
   const float wq_s = p.wq_scale[0], wo_s = p.wo_scale[0];
   const float inv_qkv = 1.0f / (ps * wq_s);
-  const float sc_g = lb_scale(amax_record_read(p.rec_dy));
+  const float sc_g = tf_scale(amax_record_read(p.rec_dy));
   const float inv_do = 1.0f / (sc_g * wo_s);
   const float inv_scale = 1.0f / p.scale;
   float sc_o = 0x1p100f, sc_q = 0x1p100f, sc_k = 0x1p100f, sc_v = 0x1p100f;      // running plane scales (attn_fused_bwd.hip)
 
   f32x16 dwq[3][2], dwo[2];
 #pragma unroll
-  for (int ti = 0; ti < 3; ++ti) { dwq[ti][0] = lb_zero(); dwq[ti][1] = lb_zero(); }
-  dwo[0] = lb_zero(); dwo[1] = lb_zero();
+  for (int ti = 0; ti < 3; ++ti) { dwq[ti][0] = tf_zero(); dwq[ti][1] = tf_zero(); }
+  dwo[0] = tf_zero(); dwo[1] = tf_zero();
   float4 dgacc = make_float4(0.f, 0.f, 0.f, 0.f), dbacc = dgacc;
   float am = 0.f;
   __syncthreads();
@@ -368,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
         KM[li] = ks[li]; KZ[li] = ks[32 + li];
         KT[li] = p.tvec[(unit * TF_HEADS + h) * 32 + li];
       }
-      lb_fit(sc_o, p.scale * tf_wave_max(amc), dwo[0], dwo[1], li, hh);        // |out[e]| <= max|ctx| sum_d qs[d] = scale max|ctx|
+      tf_fit(sc_o, p.scale * tf_wave_max(amc), dwo[0], dwo[1], li, hh);        // |out[e]| <= max|ctx| sum_d qs[d] = scale max|ctx|
     }
     const float* xu = p.x + unit * p.n_tok * TF_C;
     const float* gu = p.dy + unit * p.n_tok * TF_C;
@@ -386,10 +273,10 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
     for (int tile = tile0; tile < tile1; ++tile) {
       // ---- rows -> LayerNorm -> planes of xn; planes of dy; db_out
       float mean0, mean1, rs0, rs1;
-      lb_ln_row(nx0, g4, p.eps, ps, XH, XL, lrow, lc4, mean0, rs0);
-      lb_ln_row(nx1, g4, p.eps, ps, XH, XL, 16 + lrow, lc4, mean1, rs1);
-      lb_plane_row(ng0, sc_g, GH, GL, lrow, lc4);
-      lb_plane_row(ng1, sc_g, GH, GL, 16 + lrow, lc4);
+      tf_ln_row(nx0, g4, p.eps, ps, XH, XL, lrow, lc4, mean0, rs0);
+      tf_ln_row(nx1, g4, p.eps, ps, XH, XL, 16 + lrow, lc4, mean1, rs1);
+      tf_plane_row(ng0, sc_g, GH, GL, lrow, lc4);
+      tf_plane_row(ng1, sc_g, GH, GL, 16 + lrow, lc4);
       dbacc.x += ng0.x + ng1.x; dbacc.y += ng0.y + ng1.y; dbacc.z += ng0.z + ng1.z; dbacc.w += ng0.w + ng1.w;
       half8 woth[4], wotl[4];
 #pragma unroll
@@ -399,25 +286,25 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
       }
       __syncthreads();                                                          // B1: planes (and, at the first tile of an item, the tables)
       // ---- (q | k | v)^T of this head, dout^T
-      f32x16 aq = lb_zero(), ak = lb_zero(), av = lb_zero(), dOT = lb_zero();
+      f32x16 aq = tf_zero(), ak = tf_zero(), av = tf_zero(), dOT = tf_zero();
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const half8 bh = *reinterpret_cast<const half8*>(XH + li * TF_AST + 16 * s + 8 * hh);
         const half8 bl = *reinterpret_cast<const half8*>(XL + li * TF_AST + 16 * s + 8 * hh);
-        const int o0 = lb_woff(h * 32 + li, 2 * s + hh);
-        aq = lb_mfma3(*reinterpret_cast<const half8*>(WH + o0), *reinterpret_cast<const half8*>(WL + o0), bh, bl, aq);
-        ak = lb_mfma3(*reinterpret_cast<const half8*>(WH + o0 + TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + TF_HD * TF_C), bh, bl, ak);
-        av = lb_mfma3(*reinterpret_cast<const half8*>(WH + o0 + 2 * TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + 2 * TF_HD * TF_C), bh, bl, av);
+        const int o0 = tf_woff(h * 32 + li, 2 * s + hh);
+        aq = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0), *reinterpret_cast<const half8*>(WL + o0), bh, bl, aq);
+        ak = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0 + TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + TF_HD * TF_C), bh, bl, ak);
+        av = tf_mfma3(*reinterpret_cast<const half8*>(WH + o0 + 2 * TF_HD * TF_C), *reinterpret_cast<const half8*>(WL + o0 + 2 * TF_HD * TF_C), bh, bl, av);
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const half8 bh = *reinterpret_cast<const half8*>(GH + li * TF_AST + 16 * s + 8 * hh);
         const half8 bl = *reinterpret_cast<const half8*>(GL + li * TF_AST + 16 * s + 8 * hh);
-        dOT = lb_mfma3(woth[s], wotl[s], bh, bl, dOT);
+        dOT = tf_mfma3(woth[s], wotl[s], bh, bl, dOT);
       }
 #pragma unroll
       for (int e = 0; e < 16; ++e) { aq[e] *= inv_qkv; ak[e] *= inv_qkv; av[e] *= inv_qkv; dOT[e] *= inv_do; }
-      lb_softmax_d(aq, p.scale);                                                // aq = qs
+      tf_softmax_d(aq, p.scale);                                                // aq = qs
 #pragma unroll
       for (int c = 0; c < 4; ++c) {                                             // ak = ks = exp(k - max_n k) / Z
         const float4 m4 = *reinterpret_cast<const float4*>(KM + 8 * c + 4 * hh), z4 = *reinterpret_cast<const float4*>(KZ + 8 * c + 4 * hh);
@@ -425,19 +312,19 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
         ak[4 * c + 2] = expf(ak[4 * c + 2] - m4.z) * z4.z; ak[4 * c + 3] = expf(ak[4 * c + 3] - m4.w) * z4.w;
       }
       half8 dh[2], dl[2];
-      f32x16 dxs0 = lb_zero(), dxs1 = lb_zero();
+      f32x16 dxs0 = tf_zero(), dxs1 = tf_zero();
       auto grad_products = [&](f32x16& w0, f32x16& w1, float sc, int fbase) {
-        const half8 a0h = lb_trf(PH, LB_PS, 0, 0, lane), a0l = lb_trf(PL, LB_PS, 0, 0, lane);
-        const half8 a1h = lb_trf(PH, LB_PS, 16, 0, lane), a1l = lb_trf(PL, LB_PS, 16, 0, lane);
-        w0 = lb_mfma3(a0h, a0l, lb_trf(XH, TF_AST, 0, 0, lane), lb_trf(XL, TF_AST, 0, 0, lane), w0);
-        w0 = lb_mfma3(a1h, a1l, lb_trf(XH, TF_AST, 16, 0, lane), lb_trf(XL, TF_AST, 16, 0, lane), w0);
-        w1 = lb_mfma3(a0h, a0l, lb_trf(XH, TF_AST, 0, 32, lane), lb_trf(XL, TF_AST, 0, 32, lane), w1);
-        w1 = lb_mfma3(a1h, a1l, lb_trf(XH, TF_AST, 16, 32, lane), lb_trf(XL, TF_AST, 16, 32, lane), w1);
-        f32x16 d0 = lb_zero(), d1 = lb_zero();
+        const half8 a0h = lb_trf(PH, TF_PS, 0, 0, lane), a0l = lb_trf(PL, TF_PS, 0, 0, lane);
+        const half8 a1h = lb_trf(PH, TF_PS, 16, 0, lane), a1l = lb_trf(PL, TF_PS, 16, 0, lane);
+        w0 = tf_mfma3(a0h, a0l, lb_trf(XH, TF_AST, 0, 0, lane), lb_trf(XL, TF_AST, 0, 0, lane), w0);
+        w0 = tf_mfma3(a1h, a1l, lb_trf(XH, TF_AST, 16, 0, lane), lb_trf(XL, TF_AST, 16, 0, lane), w0);
+        w1 = tf_mfma3(a0h, a0l, lb_trf(XH, TF_AST, 0, 32, lane), lb_trf(XL, TF_AST, 0, 32, lane), w1);
+        w1 = tf_mfma3(a1h, a1l, lb_trf(XH, TF_AST, 16, 32, lane), lb_trf(XL, TF_AST, 16, 32, lane), w1);
+        f32x16 d0 = tf_zero(), d1 = tf_zero();
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          d0 = lb_mfma3(lb_wtr(WH, fbase + 16 * s, 0, lane), lb_wtr(WL, fbase + 16 * s, 0, lane), dh[s], dl[s], d0);
-          d1 = lb_mfma3(lb_wtr(WH, fbase + 16 * s, 1, lane), lb_wtr(WL, fbase + 16 * s, 1, lane), dh[s], dl[s], d1);
+          d0 = tf_mfma3(tf_wtr(WH, fbase + 16 * s, 0, lane), tf_wtr(WL, fbase + 16 * s, 0, lane), dh[s], dl[s], d0);
+          d1 = tf_mfma3(tf_wtr(WH, fbase + 16 * s, 1, lane), tf_wtr(WL, fbase + 16 * s, 1, lane), dh[s], dl[s], d1);
         }
         const float inv = 1.0f / (sc * wq_s);
 #pragma unroll
@@ -446,14 +333,14 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
       // ---- out^T = ctx^T qs^T -> dW_out[c][32 h + e] += sum_tok dy[tok][c] out[tok][e]
       {
         const f32x16 oT = lb_product16(ctxf, aq);
-        lb_split16(oT, sc_o, dh, dl, PH, PL, li, hh);
+        tf_split16<32>(oT, sc_o, dh, dl, PH, PL, li, hh);
         LB_FENCE();
-        const half8 b0h = lb_trf(PH, LB_PS, 0, 0, lane), b0l = lb_trf(PL, LB_PS, 0, 0, lane);
-        const half8 b1h = lb_trf(PH, LB_PS, 16, 0, lane), b1l = lb_trf(PL, LB_PS, 16, 0, lane);
+        const half8 b0h = lb_trf(PH, TF_PS, 0, 0, lane), b0l = lb_trf(PL, TF_PS, 0, 0, lane);
+        const half8 b1h = lb_trf(PH, TF_PS, 16, 0, lane), b1l = lb_trf(PL, TF_PS, 16, 0, lane);
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
-          dwo[ct] = lb_mfma3(lb_trf(GH, TF_AST, 0, 32 * ct, lane), lb_trf(GL, TF_AST, 0, 32 * ct, lane), b0h, b0l, dwo[ct]);
-          dwo[ct] = lb_mfma3(lb_trf(GH, TF_AST, 16, 32 * ct, lane), lb_trf(GL, TF_AST, 16, 32 * ct, lane), b1h, b1l, dwo[ct]);
+          dwo[ct] = tf_mfma3(lb_trf(GH, TF_AST, 0, 32 * ct, lane), lb_trf(GL, TF_AST, 0, 32 * ct, lane), b0h, b0l, dwo[ct]);
+          dwo[ct] = tf_mfma3(lb_trf(GH, TF_AST, 16, 32 * ct, lane), lb_trf(GL, TF_AST, 16, 32 * ct, lane), b1h, b1l, dwo[ct]);
         }
       }
       LB_FENCE();
@@ -470,8 +357,8 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
         sm = (s0 + s1) * inv_scale;
 #pragma unroll
         for (int e = 0; e < 16; ++e) dq[e] = aq[e] * (dq[e] - sm);
-        lb_fit(sc_q, tf_wave_max(lb_absmax16(dq)), dwq[0][0], dwq[0][1], li, hh);
-        lb_split16(dq, sc_q, dh, dl, PH, PL, li, hh);
+        tf_fit(sc_q, tf_wave_max(tf_absmax16(dq)), dwq[0][0], dwq[0][1], li, hh);
+        tf_split16<32>(dq, sc_q, dh, dl, PH, PL, li, hh);
         LB_FENCE();
         grad_products(dwq[0][0], dwq[0][1], sc_q, h * 32);
       }
@@ -487,8 +374,8 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
           dk[4 * c] = ak[4 * c] * (dk[4 * c] - t4.x); dk[4 * c + 1] = ak[4 * c + 1] * (dk[4 * c + 1] - t4.y);
           dk[4 * c + 2] = ak[4 * c + 2] * (dk[4 * c + 2] - t4.z); dk[4 * c + 3] = ak[4 * c + 3] * (dk[4 * c + 3] - t4.w);
         }
-        lb_fit(sc_k, tf_wave_max(lb_absmax16(dk)), dwq[1][0], dwq[1][1], li, hh);
-        lb_split16(dk, sc_k, dh, dl, PH, PL, li, hh);
+        tf_fit(sc_k, tf_wave_max(tf_absmax16(dk)), dwq[1][0], dwq[1][1], li, hh);
+        tf_split16<32>(dk, sc_k, dh, dl, PH, PL, li, hh);
         LB_FENCE();
         grad_products(dwq[1][0], dwq[1][1], sc_k, TF_HD + h * 32);
       }
@@ -500,8 +387,8 @@ __global__ __launch_bounds__(256, 1) void lattn_fused_bwd_kernel(LBwdP p) {
       // ---- dv^T = dctx^T ks^T
       {
         const f32x16 dv = lb_product16(dcf, ak);
-        lb_fit(sc_v, tf_wave_max(lb_absmax16(dv)), dwq[2][0], dwq[2][1], li, hh);
-        lb_split16(dv, sc_v, dh, dl, PH, PL, li, hh);
+        tf_fit(sc_v, tf_wave_max(tf_absmax16(dv)), dwq[2][0], dwq[2][1], li, hh);
+        tf_split16<32>(dv, sc_v, dh, dl, PH, PL, li, hh);
         LB_FENCE();
         grad_products(dwq[2][0], dwq[2][1], sc_v, 2 * TF_HD + h * 32);
       }
@@ -598,25 +485,6 @@ __global__ __launch_bounds__(256) void lattn_fused_reduce_kernel(const float* __
   }
 }
 
-static int lb_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-static int lb_chunks(int64_t units, int n_tok) {          // as linattn_fused.hip: lf_chunks
-  const int ntiles = (n_tok + 31) / 32;
-  int64_t c = (3 * (int64_t)lb_num_cus() + units - 1) / units;
-  if (c > ntiles / 2) c = ntiles / 2;
-  if (c < 1) c = 1;
-  if (c > 64) c = 64;
-  return (int)c;
-}
-
 // pass 2 runs one block per CU over (frame, chunk) items: the cut that minimises the tiles of the busiest block -- 192 frames of 50 tiles on
 // 256 CUs: 3 chunks = 576 items = 2.25 per block (a quarter of the blocks take three: 51 tiles against 37.5 on average), 4 chunks = exactly three
 // items of 11 .. 13 tiles per block (39)
@@ -632,7 +500,7 @@ static int lb_chunks2(int64_t units, int n_tok, int64_t grid) {
 }
 extern "C" int wdno_lattn_fused_bwd_grads(void) { return LB_E; }
 extern "C" size_t wdno_lattn_fused_bwd_ws_bytes(int64_t units, int n_tok) {
-  return ((size_t)units * lb_chunks(units, n_tok) * TF_HEADS * 1024 + (size_t)units * TF_HEADS * (1024 + 32) + (size_t)lb_num_cus() * LB_E) * sizeof(float);
+  return ((size_t)units * lf_chunks(units, n_tok) * TF_HEADS * 1024 + (size_t)units * TF_HEADS * (1024 + 32) + (size_t)wdno_num_cus() * LB_E) * sizeof(float);
 }
 extern "C" int wdno_lattn_fused_bwd(const float* x, const float* dy, const float* gamma, float eps, const void* wq_hi, const void* wq_lo,
                                     const float* wq_scale, const void* wot_hi, const void* wot_lo, const float* wot_scale, const float* ctx,
@@ -647,7 +515,7 @@ extern "C" int wdno_lattn_fused_bwd(const float* x, const float* dy, const float
   p.wq_hi = (const _Float16*)wq_hi; p.wq_lo = (const _Float16*)wq_lo; p.wq_scale = wq_scale;
   p.wo_hi = (const _Float16*)wot_hi; p.wo_lo = (const _Float16*)wot_lo; p.wo_scale = wot_scale;
   p.ctx = ctx; p.kstat = kstat; p.rec_dy = rec_dy;
-  p.n_tok = n_tok; p.chunks = lb_chunks(units, n_tok); p.units = units; p.scale = scale;
+  p.n_tok = n_tok; p.chunks = lf_chunks(units, n_tok); p.units = units; p.scale = scale;
   const int ntiles = (n_tok + 31) / 32;
   p.tiles_per_chunk = (ntiles + p.chunks - 1) / p.chunks;
   float* w = (float*)ws;
@@ -658,7 +526,7 @@ extern "C" int wdno_lattn_fused_bwd(const float* x, const float* dy, const float
   p.dx = dx; p.amax_rec = amax_rec;
   const int64_t nitems = units * p.chunks;
   if (nitems > 0x7fffffff) return WDNO_EUNSUPPORTED;
-  p.chunks2 = lb_chunks2(units, n_tok, lb_num_cus());
+  p.chunks2 = lb_chunks2(units, n_tok, wdno_num_cus());
   p.tiles_per_chunk2 = (ntiles + p.chunks2 - 1) / p.chunks2;
   const int64_t nitems2 = units * p.chunks2;
   static bool attr_done = false;
@@ -669,7 +537,7 @@ extern "C" int wdno_lattn_fused_bwd(const float* x, const float* dy, const float
   hipStream_t st = as_stream(s);
   lattn_fused_dctx_kernel<<<(unsigned)nitems, 256, 0, st>>>(p);
   lattn_fused_dctx_merge_kernel<<<(unsigned)(units * TF_HEADS), 256, 0, st>>>(p.part1, ctx, p.dctx, p.tvec, p.chunks);
-  int64_t grid = lb_num_cus();
+  int64_t grid = wdno_num_cus();
   if (grid > nitems2) grid = nitems2;
   lattn_fused_bwd_kernel<<<(unsigned)grid, 256, LB_LDS_BYTES, st>>>(p);
   lattn_fused_reduce_kernel<<<(LB_E + 31) / 32, 256, 0, st>>>(p.part2, (int)grid, grads, LB_E);

@@ -12,49 +12,10 @@
 // hh = channels 32 t + 16 hh .. + 15; and to_out
 // contracts over all 128 features per wave (wave w = output channels w C/4 ..) from (hi, lo) planes of the four heads' out tiles in LDS
 // under ONE scale (scale x max|ctx| over the heads of the frame) instead of summing per-head partial tiles.
+// Lane-level steps (tf_ln_row_wide, tf_plane_scale_wide, tf_softmax_d, the fragment loads and waits) are in attn_fused.h; LW_ names are this file's.
 #include "linattn_fused.h"
 
 #define LW_OST 136    /* halves per token row of an out plane (128 features + 8) */
-
-// one row of C channels by its 16 lanes: LayerNorm (gain re-read per row: L1 hits) -> (hi, lo) planes
-template <int C>
-__device__ __forceinline__ void lw_ln_row(const float4 (&xin)[C / 64], const float* __restrict__ gamma, float eps, float ps, _Float16* __restrict__ Ah,
-                                          _Float16* __restrict__ Al, int row, int lc4) {
-  constexpr int NJ = C / 64, AST = C + 8;
-  float4 xv[NJ];
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) { xv[j] = xin[j]; s += (xv[j].x + xv[j].y) + (xv[j].z + xv[j].w); }
-  const float mean = tf_row16_sum(s) * (1.0f / C);
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    xv[j].x -= mean; xv[j].y -= mean; xv[j].z -= mean; xv[j].w -= mean;
-    q += (xv[j].x * xv[j].x + xv[j].y * xv[j].y) + (xv[j].z * xv[j].z + xv[j].w * xv[j].w);
-  }
-  const float rstd = 1.0f / sqrtf(tf_row16_sum(q) * (1.0f / C) + eps);
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const float4 g = reinterpret_cast<const float4*>(gamma)[16 * j + lc4];
-    const float o[4] = {xv[j].x * rstd * g.x, xv[j].y * rstd * g.y, xv[j].z * rstd * g.z, xv[j].w * rstd * g.w};
-    half4v hv, lv;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float t = o[e] * ps;
-      hv[e] = (_Float16)t;
-      lv[e] = (_Float16)(t - (float)hv[e]);
-    }
-    *reinterpret_cast<half4v*>(Ah + row * AST + 64 * j + 4 * lc4) = hv;
-    *reinterpret_cast<half4v*>(Al + row * AST + 64 * j + 4 * lc4) = lv;
-  }
-}
-template <int C>
-__device__ __forceinline__ float lw_plane_scale(const float* __restrict__ gamma, int lc4) {      // |LayerNorm(x)| <= sqrt(C) max|g|
-  float gm = 0.f;
-#pragma unroll
-  for (int j = 0; j < C / 64; ++j) gm = amax4(gm, reinterpret_cast<const float4*>(gamma)[16 * j + lc4]);
-  return scale_from_amax(sqrtf((float)C) * group_max<16>(gm));
-}
 
 // ------------------------------------------------------------------------------------------------ pass 1: per-chunk context
 template <int C>
@@ -72,7 +33,7 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_ctx_kernel(LFusedP p) {
   // k rows (ti = 1) and v rows (ti = 2) of this head, as the COLUMN operand of the swapped product: + ((ti NP + t) 2 + s) 512
   const unsigned wq_off = (unsigned)(h * 3 * NP * 2 * 64 + lane) * 16u;      // bytes
   const __amdgpu_buffer_rsrc_t rqh = tf_rsrc(p.wq_hi, 3 * TF_HD * C * 2), rql = tf_rsrc(p.wq_lo, 3 * TF_HD * C * 2);
-  const float ps = lw_plane_scale<C>(p.gamma, lc4);
+  const float ps = tf_plane_scale_wide<C>(p.gamma, lc4);
   const float inv_qkv = 1.0f / (ps * p.wq_scale[0]);
   const float* xu = p.x + (int64_t)unit * p.n_tok * C;
   const int tile0 = chunk * p.tiles_per_chunk;
@@ -80,7 +41,7 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_ctx_kernel(LFusedP p) {
   const int tile1 = min(ntiles, tile0 + p.tiles_per_chunk);
 
   float m_run = -INFINITY, z_run = 0.f;                 // feature d = li: running maximum over the tokens so far, partial sum of this lane half
-  f32x16 ctx = lf_zero();                               // ctx_raw[d][e]: lane (e, hh), register r <-> d = tf_key(r, hh)
+  f32x16 ctx = tf_zero();                               // ctx_raw[d][e]: lane (e, hh), register r <-> d = tf_key(r, hh)
   float4 nx0[NJ], nx1[NJ];
   auto fetch = [&](int tile) {
     const int r0 = tile * 32 + lrow, r1 = r0 + 16;
@@ -92,11 +53,11 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_ctx_kernel(LFusedP p) {
   };
   if (tile0 < tile1) fetch(tile0);
   for (int tile = tile0; tile < tile1; ++tile) {
-    lw_ln_row<C>(nx0, p.gamma, p.eps, ps, Ah, Al, lrow, lc4);
-    lw_ln_row<C>(nx1, p.gamma, p.eps, ps, Ah, Al, 16 + lrow, lc4);
+    tf_ln_row_wide<C>(nx0, p.gamma, p.eps, ps, Ah, Al, lrow, lc4);
+    tf_ln_row_wide<C>(nx1, p.gamma, p.eps, ps, Ah, Al, 16 + lrow, lc4);
     __syncthreads();
     // k[tok][d], v[tok][e] of the tile: rows = tokens (A = the token planes), columns = features (B = the streamed weight rows)
-    f32x16 ak = lf_zero(), av = lf_zero();
+    f32x16 ak = tf_zero(), av = tf_zero();
     {
       half8 w0[2][2][2], w1[2][2][2];                   // [k | v][hi | lo][step]
       auto wload = [&](half8 (&w)[2][2][2], int t) {
@@ -112,8 +73,8 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_ctx_kernel(LFusedP p) {
         for (int s = 0; s < 2; ++s) {
           const half8 ah = *reinterpret_cast<const half8*>(Ah + li * AST + 32 * t + 16 * hh + 8 * s);
           const half8 al = *reinterpret_cast<const half8*>(Al + li * AST + 32 * t + 16 * hh + 8 * s);
-          ak = lf_mfma3(ah, al, w[0][0][s], w[0][1][s], ak);
-          av = lf_mfma3(ah, al, w[1][0][s], w[1][1][s], av);
+          ak = tf_mfma3(ah, al, w[0][0][s], w[0][1][s], ak);
+          av = tf_mfma3(ah, al, w[1][0][s], w[1][1][s], av);
         }
       };
       // No fragment load is in flight while the matrix instructions of a pair run (attn_fused.h: the hand-over note): both sets are
@@ -204,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_out_kernel(LFusedP p) {
   // |out[e]| <= max_d |ctx[d][e]| sum_d qs[d] = scale max|ctx|; one scale for the four heads' tiles (they share the reduction of to_out)
   const float so = scale_from_amax(p.scale * fmaxf(fmaxf(Cmax[0], Cmax[1]), fmaxf(Cmax[2], Cmax[3])));
   const float inv_o = 1.0f / (so * p.wo_scale[0]);
-  const float ps = lw_plane_scale<C>(p.gamma, lc4);
+  const float ps = tf_plane_scale_wide<C>(p.gamma, lc4);
   const float inv_qkv = 1.0f / (ps * p.wq_scale[0]);
   const float* xu = p.x + (int64_t)unit * p.n_tok * C;
   float* yu = p.y + (int64_t)unit * p.n_tok * C;
@@ -223,11 +184,11 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_out_kernel(LFusedP p) {
   };
   if (tile0 < tile1) fetch(tile0);
   for (int tile = tile0; tile < tile1; ++tile) {
-    lw_ln_row<C>(nx0, p.gamma, p.eps, ps, Ah, Al, lrow, lc4);
-    lw_ln_row<C>(nx1, p.gamma, p.eps, ps, Ah, Al, 16 + lrow, lc4);
+    tf_ln_row_wide<C>(nx0, p.gamma, p.eps, ps, Ah, Al, lrow, lc4);
+    tf_ln_row_wide<C>(nx1, p.gamma, p.eps, ps, Ah, Al, 16 + lrow, lc4);
     __syncthreads();                                                                  // S1: planes of this tile complete
     // q^T of the head: [feature][token], a lane owns one token and the features 8 c + 4 hh + (0..3)
-    f32x16 aq = lf_zero();
+    f32x16 aq = tf_zero();
     {
       half8 w0[2][2], w1[2][2];                          // [hi | lo][step]
       auto wload = [&](half8 (&w)[2][2], int t) {
@@ -240,7 +201,7 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_out_kernel(LFusedP p) {
         for (int s = 0; s < 2; ++s) {
           const half8 bh = *reinterpret_cast<const half8*>(Ah + li * AST + 32 * t + 16 * hh + 8 * s);
           const half8 bl = *reinterpret_cast<const half8*>(Al + li * AST + 32 * t + 16 * hh + 8 * s);
-          aq = lf_mfma3(w[0][s], w[1][s], bh, bl, aq);
+          aq = tf_mfma3(w[0][s], w[1][s], bh, bl, aq);
         }
       };
 #pragma unroll 1
@@ -256,24 +217,11 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_out_kernel(LFusedP p) {
     }
     if (tile + 1 < tile1) fetch(tile + 1);
     // qs = scale softmax over the head's 32 features of the token (16 here, 16 in lane ^ 32)
-    {
-      float mx = -INFINITY;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) { aq[e] *= inv_qkv; mx = fmaxf(mx, aq[e]); }
-      float m0, m1;
-      tf_halves(mx, m0, m1);
-      mx = fmaxf(m0, m1);
-      float l = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { aq[e] = expf(aq[e] - mx); l += aq[e]; }
-      float l0, l1;
-      tf_halves(l, l0, l1);
-      const float il = p.scale / (l0 + l1);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) aq[e] *= il;
-    }
+    for (int e = 0; e < 16; ++e) aq[e] *= inv_qkv;
+    tf_softmax_d(aq, p.scale);
     // out^T[e][tok] = sum_d ctx[d][e] qs[tok][d] (exact fp32, qs in place)
-    f32x16 oT = lf_zero();
+    f32x16 oT = tf_zero();
 #pragma unroll
     for (int r = 0; r < 16; ++r) oT = __builtin_amdgcn_mfma_f32_32x32x2f32(ctxf[r], aq[r], oT, 0, 0, 0);
     // (hi, lo) planes of the head's out tile: lane (token li, hh) owns features 8 c + 4 hh + (0..3)
@@ -295,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_out_kernel(LFusedP p) {
     const bool tok = tk < p.n_tok;
 #pragma unroll 1
     for (int mt = 0; mt < MT; ++mt) {
-      f32x16 y = lf_zero();
+      f32x16 y = tf_zero();
       half8 u0[2][2], u1[2][2];
       auto uload = [&](half8 (&u)[2][2], int t) {
         const unsigned o = (unsigned)(mt * 4 + t) * 2048u;
@@ -307,7 +255,7 @@ __global__ __launch_bounds__(256, 2) void lattn_wide_out_kernel(LFusedP p) {
         for (int s = 0; s < 2; ++s) {
           const half8 oh = *reinterpret_cast<const half8*>(Oh + li * LW_OST + 32 * t + 16 * hh + 8 * s);
           const half8 ol = *reinterpret_cast<const half8*>(Ol + li * LW_OST + 32 * t + 16 * hh + 8 * s);
-          y = lf_mfma3(u[0][s], u[1][s], oh, ol, y);
+          y = tf_mfma3(u[0][s], u[1][s], oh, ol, y);
         }
       };
 #pragma unroll 1
