@@ -601,6 +601,41 @@ typedef struct {
 } wdno_burgers_desc;
 int wdno_burgers_solve(const float* u0, const float* f, float* out, const wdno_burgers_desc* d, wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ Burgers control-objective guidance
+ * The gradient of the control objective of the Burgers evaluation (eval_ddpm_burgers.py:108-147 get_loss_fn_2dconv / get_nablaJ_2dconv,
+ * test_util.py:100-126 ddpm_guidance_loss) in closed form, one launch. For a network-unit tensor x [B][C][H][W] (C >= 8):
+ *   coef = (x RESCALER)[:, 0:8, :h, :w]   (channels 0-3 = LL, da, ad, dd of u, 4-7 of f: wave_trans.py:30-40)
+ *   u_f  = IDWT2(coef)[:, :, :n_t, :n_x]  (H pass, then W pass);  u = u_f[:, 0], f = u_f[:, 1, :n_t - 1]
+ *   J    = wu (sum_b mean_x[(u[b,0] - target[b,0])^2 + (1 - condition_f) (u[b,n_t-1] - target[b,1])^2] + wf sum f^2)
+ * J is quadratic and the synthesis linear, so with the residual r (2 wu (u - target) / n_x on rows 0 and n_t - 1 of field u, 2 wu wf f
+ * on rows < n_t - 1 of field f, 0 elsewhere on the 2h x 2w grid)  g = dJ/dx = RESCALER IDWT2^T(r)  on [:, 0:8, :h, :w] and exactly 0
+ * elsewhere (RESCALER once: the reference differentiates with respect to the unscaled x, model_utils.py:35-50).
+ *   x_t != NULL (fused mode, one sampling step, diffusion_1d.py:205-227): in = eps, x0 = c1[t_b] x_t - c2[t_b] eps (clamped to [-1, 1]
+ *     when clip_x0), out = eps + g(x0) s_table[t_b] -- a product then a sum, two roundings; out = eps bit for bit wherever g is
+ *     structurally 0. The reference reads its schedule at t[0] for the whole batch (diffusion_1d.py:222); its samplers pass one t per
+ *     batch, so indexing s_table per sample like c1 / c2 is the same thing. t_b is clamped into [0, num_timesteps).
+ *   x_t == NULL (gradient mode): in = x0, out = g; t, c1, c2, s_table are not read.
+ * target [B][2][n_x]: rows 0 and n_t - 1 of u_target. filt: host pointer to (dec_lo, dec_hi, rec_lo, rec_hi), L taps each, as wdno_dwt_*.
+ * Grid: 1 + ntile workgroups per sample -- one for field u (only reconstruction rows 0 and n_t - 1 and the coefficient rows within
+ * the filter's reach of them are computed) and ntile column tiles of tw coefficient columns (plus L/2 - 1 halo columns each side, periodic)
+ * for field f; every intermediate lives in lds_bytes of LDS (no workspace). No atomics, every sum in a fixed order: a sample's result does
+ * not depend on B or its index. `in` and `out` must not overlap (a tile reads its neighbours' halo columns). ntile tw >= w, lds_bytes <= 64 KiB and what the layout needs
+ * (wdno_amd/burgers/guidance.py: plan); WDNO_EUNSUPPORTED for anything but mode 0 (periodization) with L = 10 (bior2.4),
+ * WDNO_EINVAL for inconsistent integers. */
+typedef struct {
+  int B, C, H, W;                                  /* the tensors x_t, in, out */
+  int sample_stride, chan_stride, row_stride;      /* in elements; columns are contiguous */
+  int h, w, n_t, n_x;                              /* coefficient block (padded_shape) and field size (ori_shape): n_t <= 2h, n_x <= 2w */
+  int L, mode;
+  int ntile, tw, lds_bytes;
+  int num_timesteps;                               /* length of c1, c2, s_table */
+  int condition_f, clip_x0;
+  float wu, wf;
+} wdno_burgers_guidance_desc;
+int wdno_burgers_guidance(const float* x_t, const float* in, const int64_t* t, const float* c1, const float* c2, const float* s_table,
+                          const float* rescaler, const float* target, float* out, const wdno_burgers_guidance_desc* d, const float* filt,
+                          wdno_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,11 @@ class BurgersDesc(C.Structure):             # include/wdno_hip.h: wdno_burgers_d
                                  'points')] + [(k, F) for k in ('c', 'd', 'dm', 'dt')]
 
 
+class BurgersGuidanceDesc(C.Structure):     # include/wdno_hip.h: wdno_burgers_guidance_desc
+    _fields_ = [(k, I) for k in ('B', 'C', 'H', 'W', 'sample_stride', 'chan_stride', 'row_stride', 'h', 'w', 'n_t', 'n_x', 'L', 'mode', 'ntile',
+                                 'tw', 'lds_bytes', 'num_timesteps', 'condition_f', 'clip_x0')] + [(k, F) for k in ('wu', 'wf')]
+
+
 PD, PG, PA, PC = C.POINTER(DwtDesc), C.POINTER(ConvGeom), C.POINTER(AttnDesc), C.POINTER(CondDesc)
 PF = C.POINTER(C.c_float)
 
@@ -183,6 +188,7 @@ PROTOTYPES = {
     'wdno_relpos_bias_fwd': (I, [P, P, P, I, I, P]),
     'wdno_relpos_bias_bwd': (I, [P, P, P, I, I, I, P]),
     'wdno_burgers_solve': (I, [P, P, P, C.POINTER(BurgersDesc), P]),
+    'wdno_burgers_guidance': (I, [P, P, P, P, P, P, P, P, P, C.POINTER(BurgersGuidanceDesc), PF, P]),
 }
 
 _lib = None

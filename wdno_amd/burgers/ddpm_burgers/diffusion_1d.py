@@ -208,6 +208,19 @@ class GaussianDiffusion(nn.Module):
         the fused posterior / DDIM update launches take the U-Net output as the noise estimate."""
         return self.objective != 'pred_noise' or any(kwargs.get(k) is not None for k in ('nablaJ', 'pred_noise'))
 
+    def _graph_guidance(self, kwargs):
+        """Guidance the fused, graph-replayed loop takes (K.guided_sampling_loop_burgers): a `graph_safe` objective with a fused step
+        (burgers/guidance.py: BurgersGuidance), the default projection eps + nablaJ s, the U-Net's own noise estimate. Everything else --
+        plain callables, a custom proj_guidance, an injected pred_noise, pred_x0 / pred_v, self-conditioning -- keeps the general form."""
+        nabla_J = kwargs.get('nablaJ')
+        return (self.objective == 'pred_noise' and nabla_J is not None and bool(getattr(nabla_J, 'graph_safe', False))
+                and hasattr(nabla_J, 'guide') and kwargs.get('proj_guidance') is None and kwargs.get('pred_noise') is None
+                and not self.self_condition)
+
+    def _guided_loop(self, img, src, desc, kwargs, **loop):
+        s_table = K.guidance_s_table(kwargs.get('J_scheduler'), self.num_timesteps)
+        return K.guided_sampling_loop_burgers(self, img, src, desc, kwargs['nablaJ'], s_table, use_graph=self.use_graph, **loop)
+
     @torch.no_grad()
     def p_sample(self, x, t: int, x_self_cond=None, **kwargs):
         b, device = x.shape[0], x.device
@@ -255,6 +268,8 @@ class GaussianDiffusion(nn.Module):
         img = self.sample_noise(shape, device).contiguous()
         if not self._guided(kwargs) and not self.self_condition:   # unguided: fused launches, the step replayed from one HIP graph
             img = K.sampling_loop(self, img, src, desc, cond_first=True, use_graph=self.use_graph)
+        elif self._graph_guidance(kwargs):                         # the control objective's kernel: the same, one launch more per step
+            img = self._guided_loop(img, src, desc, kwargs)
         else:
             x_start = None
             for t in reversed(range(0, self.num_timesteps)):
@@ -274,6 +289,8 @@ class GaussianDiffusion(nn.Module):
         pairs = K.ddim_time_pairs(self.num_timesteps, self.sampling_timesteps)
         if not self._guided(kwargs) and not self.self_condition:
             img = K.sampling_loop(self, img, src, desc, ddim_pairs=pairs, eta=eta, cond_first=True, use_graph=self.use_graph)
+        elif self._graph_guidance(kwargs):
+            img = self._guided_loop(img, src, desc, kwargs, ddim_pairs=pairs, eta=eta)
         else:
             x_start = None
             for time, time_next in pairs:

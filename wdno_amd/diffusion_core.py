@@ -326,8 +326,26 @@ def _step_graph(mod, shape, desc, ddim, cond_first, device, guided_factory=None,
     return sg
 
 
-def sampling_loop(mod, x, src, desc, *, ddim_pairs=None, eta=0.0, cond_first, use_graph=None):
-    """The unguided sampling loop of both GaussianDiffusion classes (diffusion_1d.py:310-460, diffusion_2d.py:788-933).
+def guidance_s_table(J_scheduler, num_timesteps):
+    """The guidance step size of every timestep, [num_timesteps] fp32 on the host: J_scheduler(t) (None: 1) evaluated once per t and rounded
+    to fp32, which is what the reference's `nablaJ(x) * J_scheduler(t)` multiplies with (a python float or a 0-dim fp64 tensor against an
+    fp32 tensor: diffusion_1d.py:222)."""
+    if J_scheduler is None:
+        return torch.ones(num_timesteps, dtype=torch.float32)
+    return torch.tensor([float(J_scheduler(t)) for t in range(num_timesteps)], dtype=torch.float64).to(torch.float32)
+
+
+def guided_sampling_loop_burgers(mod, x, src, desc, guidance, s_table, *, ddim_pairs=None, eta=0.0, use_graph=None):
+    """The Burgers sampling loop under guidance by a `graph_safe` control objective (burgers/guidance.py: BurgersGuidance;
+    diffusion_1d.py:205-227 inside :310-460): every noisy step is apply_cond -> U-Net -> ONE guidance launch that turns eps into
+    eps + nablaJ(x0) s_table[t] -> the unguided posterior / DDIM update, replayed from one captured graph like the unguided loop; the
+    last, noise-free step is eager. s_table: guidance_s_table(J_scheduler, mod.num_timesteps)."""
+    return sampling_loop(mod, x, src, desc, ddim_pairs=ddim_pairs, eta=eta, cond_first=True, use_graph=use_graph, guidance=guidance, s_table=s_table)
+
+
+def sampling_loop(mod, x, src, desc, *, ddim_pairs=None, eta=0.0, cond_first, use_graph=None, guidance=None, s_table=None):
+    """The sampling loop of both GaussianDiffusion classes (diffusion_1d.py:310-460, diffusion_2d.py:788-933): unguided, or (guidance, s_table
+    given, Burgers order only) with the noise estimate of every step passed through guidance.guide -- see guided_sampling_loop_burgers.
 
     x: the initial draw [B, ...]; src / desc: clean values and predicate of the conditioned positions. cond_first = True is the
     Burgers order (conditions imposed before every U-Net call; the caller imposes them once more on the result), False the
@@ -346,9 +364,21 @@ def sampling_loop(mod, x, src, desc, *, ddim_pairs=None, eta=0.0, cond_first, us
         noisy = [t > 0 for t, _ in steps]
     if use_graph is None:
         use_graph = SAMPLE_GRAPH and sum(noisy) >= SAMPLE_GRAPH_MIN_STEPS
-    sg = None
+    sg, gkw, s_dev = None, {}, None
+    if guidance is not None:
+        assert cond_first, 'guidance launches are part of the Burgers step order only'
+        s_dev = s_table.to(dev, torch.float32).contiguous()
+
+        def guided_factory(static):
+            # the captured step reads the schedule from the graph's static buffer; the target rows live in the guidance object's own buffer
+            def guided(xx, t, noise, coef):
+                eps = guidance.guide(mod, xx, mod.model(xx, t, None), t, static['s_table'], ddim)
+                return (ddim_update_dev(mod, xx, eps, noise, t, coef) if ddim else p_sample_update(mod, xx, eps, noise, t, clamp=True))[0]
+            return guided
+        gkw = dict(guided_factory=guided_factory, guided_key=('burgers-guided', id(guidance), guidance.key()), static=dict(s_table=s_dev),
+                   keep=guidance)
     if use_graph and any(noisy):
-        sg = _step_graph(mod, shape, desc, ddim, cond_first, dev)
+        sg = _step_graph(mod, shape, desc, ddim, cond_first, dev, **gkw)
         sg.src.copy_(src)
         sg.x.copy_(x)
         if not cond_first:                        # the captured step relies on the conditions holding on its input (_StepGraph._body): make it so
@@ -371,6 +401,8 @@ def sampling_loop(mod, x, src, desc, *, ddim_pairs=None, eta=0.0, cond_first, us
             apply_cond(x, src, desc)
         bt = torch.full((b,), t, device=dev, dtype=torch.long)
         eps = mod.model(x, bt, None)
+        if guidance is not None:
+            eps = guidance.guide(mod, x, eps, bt, s_dev, ddim)      # (x0 is clamped before the gradient on the DDIM path only: clip_x_start)
         if ddim:
             if noise is None:
                 x, _ = ddim_update(mod, x, eps, None, bt, 0., 0., 0.)
