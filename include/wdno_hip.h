@@ -636,6 +636,29 @@ int wdno_burgers_guidance(const float* x_t, const float* in, const int64_t* t, c
                           const float* rescaler, const float* target, float* out, const wdno_burgers_guidance_desc* d, const float* filt,
                           wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ smoke control-evaluation solver
+ * solver() of smoke/dataset/evaluate_solver.py:135-196 for B simulations in one launch, one workgroup of `threads` (1024 or 512) threads per
+ * simulation: num_t (<= 256) frames of { velocity = interior of the previous frame's + 16-cell rim of the control (c1, c2 [B][nt][nx][nx],
+ * tiled by time_interval and space_interval), masked; divergence; the masked 5-point system solved by CG in fp32 from x = 0 until
+ * max|r| < accuracy or max_iter (<= 500) iterations, with the reference's aliased first iteration (phi/solver/base.py:56-103) and the
+ * pressure (the sum of the steps) accumulated in fp64; velocity minus
+ * the masked pressure gradient; advection of the density and the set-zero density (linear, coordinates clamped, fp64 weights); the seven
+ * fp64 bucket sums and the ratio outs[1] / (sum(outs) + sum(set-zero density)) }. A frame whose masked divergence is below `accuracy`
+ * everywhere keeps zero pressure (the reference's loop condition), and the loop also ends when sum(p Ap) is exactly zero.
+ * Geometry is data, fp32: fluid_ext, active_ext [129][129] (the masks with their boundary padding), velocity_mask [128][128][2],
+ * buckets [8][128][128] (seven bucket masks, then the set-zero mask). init_density [B][nx][nx]; init_velocity [128][128][2], shared.
+ * frame_slot [num_t]: the output slot of a frame or -1; density, zero_density [B][n_out][128][128], velocity [B][n_out][128][128][2],
+ * ratio [B][num_t] fp64 (every frame). ws: 9 * 128 * 128 floats per simulation, 16-byte aligned. Every sum has a fixed order: a simulation's result does not
+ * depend on `threads`, B or its index. WDNO_EINVAL for inconsistent integers, WDNO_EUNSUPPORTED for another `threads`. */
+typedef struct {
+  int B, nt, nx, time_interval, space_interval;
+  int num_t, max_iter, n_out, threads;
+  float accuracy;
+} wdno_smoke_solve_desc;
+int wdno_smoke_solve(const float* init_density, const float* c1, const float* c2, const float* init_velocity, const float* fluid_ext,
+                     const float* active_ext, const float* velocity_mask, const float* buckets, const int* frame_slot, float* density,
+                     float* zero_density, float* velocity, double* ratio, float* ws, const wdno_smoke_solve_desc* d, wdno_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

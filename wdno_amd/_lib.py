@@ -57,6 +57,10 @@ class BurgersGuidanceDesc(C.Structure):     # include/wdno_hip.h: wdno_burgers_g
                                  'tw', 'lds_bytes', 'num_timesteps', 'condition_f', 'clip_x0')] + [(k, F) for k in ('wu', 'wf')]
 
 
+class SmokeSolveDesc(C.Structure):          # include/wdno_hip.h: wdno_smoke_solve_desc
+    _fields_ = [(k, I) for k in ('B', 'nt', 'nx', 'time_interval', 'space_interval', 'num_t', 'max_iter', 'n_out', 'threads')] + [('accuracy', F)]
+
+
 PD, PG, PA, PC = C.POINTER(DwtDesc), C.POINTER(ConvGeom), C.POINTER(AttnDesc), C.POINTER(CondDesc)
 PF = C.POINTER(C.c_float)
 
@@ -189,6 +193,7 @@ PROTOTYPES = {
     'wdno_relpos_bias_bwd': (I, [P, P, P, I, I, I, P]),
     'wdno_burgers_solve': (I, [P, P, P, C.POINTER(BurgersDesc), P]),
     'wdno_burgers_guidance': (I, [P, P, P, P, P, P, P, P, P, C.POINTER(BurgersGuidanceDesc), PF, P]),
+    'wdno_smoke_solve': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeSolveDesc), P]),
 }
 
 _lib = None
