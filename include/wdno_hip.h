@@ -659,6 +659,35 @@ int wdno_smoke_solve(const float* init_density, const float* c1, const float* c2
                      const float* active_ext, const float* velocity_mask, const float* buckets, const int* frame_slot, float* density,
                      float* zero_density, float* velocity, double* ratio, float* ws, const wdno_smoke_solve_desc* d, wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ smoke data-set generator
+ * The training-set simulator of smoke/dataset/a_gen_train.py:363-456, 502-696 (and a_gen_test_64 / a_gen_test_128, which differ in recording
+ * only) for B scenes in one launch, one workgroup of `threads` (1024 or 512) threads per scene: frames 0..scenelength (<= 256), each with the
+ * steps of wdno_smoke_solve (same code, csrc/smoke_flow.h; the advection coordinate idx - v is formed in fp64 here, in fp32 there), but the 16-cell rim of a frame's velocity is the previous frame's projected rim
+ * plus noise, fp32(fp64(previous) + noise), or, on the scene's four kick frames, the noise field itself, fp32(noise).
+ * scene_i [B][8]: xs0, ys0 (the 11 x 11 block of initial density), the four kick frames, 0, 0. scene_v [B][8]: (vx, vy) of the four kicks.
+ * scene_index [B]: the scene's number in the data set. noise_mode 0: `noise` float64 [B][scenelength + 1][128][128][2] is read (rim cells
+ * only); noise_mode 1: noise = NULL, the field is 0.1 z (ordinary frame) or v + (|v| / 10) z (kick) in fp32 with z the Box-Muller pair
+ * (r cos, r sin; r = sqrt(-2 ln u1), angle 2 pi u2; u = ((x >> 9) + 0.5) 2^-23 of outputs 0 and 1) of Philox4x32-10 with key = seed and
+ * counter = (cell 128 i + j, frame, scene_index low, scene_index high): a scene has the same bits in any batch.
+ * Bucket rule: on the set-zero density; tested on all cells, summed on the recorded stride; on a kick frame only if the frame is recorded;
+ * never at frame 0. Records at frames k * record_scale, cells ::stride (n = 128 / stride, R = scenelength / record_scale + 1):
+ * density [B][R][n][n] (never zeroed), velocity, control [B][R][n][n][2] (control: the rim field before the mask, interior 0; velocity
+ * record 0 holds component 0 twice, as the reference writes it), smoke [B][R][8] fp64 (seven bucket totals; column 7: the strided sum of
+ * the set-zero density after zeroing on an ordinary frame, of the density on a kick frame and at frame 0). ws as for wdno_smoke_solve.
+ * wdno_smoke_noise: the noise_mode-1 fields of n <= 65535 (scene_index, frame, is_kick, kick_v (vx, vy)) items, out [n][128][128][2] fp32. */
+typedef struct {
+  int B, scenelength, record_scale, stride;
+  int max_iter, threads, noise_mode;
+  float accuracy;
+  unsigned long long seed;
+} wdno_smoke_generate_desc;
+int wdno_smoke_generate(const int* scene_i, const float* scene_v, const long long* scene_index, const double* noise,
+                        const float* init_velocity, const float* fluid_ext, const float* active_ext, const float* velocity_mask,
+                        const float* buckets, float* density, float* velocity, float* control, double* smoke, float* ws,
+                        const wdno_smoke_generate_desc* d, wdno_stream_t s);
+int wdno_smoke_noise(const long long* scene_index, const int* frame, const int* is_kick, const float* kick_v, int n,
+                     unsigned long long seed, float* out, wdno_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,10 @@ class SmokeSolveDesc(C.Structure):          # include/wdno_hip.h: wdno_smoke_sol
     _fields_ = [(k, I) for k in ('B', 'nt', 'nx', 'time_interval', 'space_interval', 'num_t', 'max_iter', 'n_out', 'threads')] + [('accuracy', F)]
 
 
+class SmokeGenerateDesc(C.Structure):       # include/wdno_hip.h: wdno_smoke_generate_desc
+    _fields_ = [(k, I) for k in ('B', 'scenelength', 'record_scale', 'stride', 'max_iter', 'threads', 'noise_mode')] + [('accuracy', F), ('seed', C.c_uint64)]
+
+
 PD, PG, PA, PC = C.POINTER(DwtDesc), C.POINTER(ConvGeom), C.POINTER(AttnDesc), C.POINTER(CondDesc)
 PF = C.POINTER(C.c_float)
 
@@ -194,6 +198,8 @@ PROTOTYPES = {
     'wdno_burgers_solve': (I, [P, P, P, C.POINTER(BurgersDesc), P]),
     'wdno_burgers_guidance': (I, [P, P, P, P, P, P, P, P, P, C.POINTER(BurgersGuidanceDesc), PF, P]),
     'wdno_smoke_solve': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeSolveDesc), P]),
+    'wdno_smoke_generate': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeGenerateDesc), P]),
+    'wdno_smoke_noise': (I, [P, P, P, P, I, C.c_uint64, P, P]),
 }
 
 _lib = None
