@@ -601,6 +601,26 @@ typedef struct {
 } wdno_burgers_desc;
 int wdno_burgers_solve(const float* u0, const float* f, float* out, const wdno_burgers_desc* d, wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ Burgers data-set generation
+ * One batch of generate_data_burgers_equation (generate_burgers.py:278-368) in one launch: the solver above on s points (u0 [N][s] dense, no
+ * interpolation) with the forcing of make_data_varying_f (l.246-273) formed from its separable parts instead of read from a dense [N][t][s]
+ * tensor: ax [N][8][s] = amp_j exp_space_j, tt [N][t][8] = exp_time_j, f[n][iv][g] = sum_j ax[n][j][g] tt[n][iv][j] with j ascending and every
+ * fp32 operation separate (the reference's bits), then clamp(f alpha, -10, 10) when `clamp` is set (alpha != 1, l.272-273).
+ * u_rec [N][num_t + 1][cols]: the columns 0, sx, 2 sx, ... of u0 and of the recorded rows (trajectory[:, :, ::sx], l.347);
+ * f_rec [N][f_rows][cols]: the forcing of the intervals 0, st, 2 st, ... at those columns (f[:, ::st, ::sx], l.346); cols = ceil(s / sx),
+ * f_rows = ceil(t / st). steps, record_time, f_time, the constants and (waves, points) as in wdno_burgers_desc, with nt_f = t; the same
+ * consistency checks (WDNO_EINVAL). The result of a trajectory does not depend on (waves, points), N or its index, and its u_rec equals
+ * wdno_burgers_solve's on the dense forcing bit for bit. */
+typedef struct {
+  int N, s, t;
+  int steps, record_time, f_time, num_t;
+  int st, sx, f_rows, cols;
+  int waves, points, clamp;
+  float c, d, dm, dt, alpha;
+} wdno_burgers_generate_desc;
+int wdno_burgers_generate(const float* u0, const float* ax, const float* tt, float* u_rec, float* f_rec,
+                          const wdno_burgers_generate_desc* d, wdno_stream_t s);
+
 /* ------------------------------------------------------------------------------------------------ Burgers control-objective guidance
  * The gradient of the control objective of the Burgers evaluation (eval_ddpm_burgers.py:108-147 get_loss_fn_2dconv / get_nablaJ_2dconv,
  * test_util.py:100-126 ddpm_guidance_loss) in closed form, one launch. For a network-unit tensor x [B][C][H][W] (C >= 8):

@@ -52,6 +52,11 @@ class BurgersDesc(C.Structure):             # include/wdno_hip.h: wdno_burgers_d
                                  'points')] + [(k, F) for k in ('c', 'd', 'dm', 'dt')]
 
 
+class BurgersGenerateDesc(C.Structure):     # include/wdno_hip.h: wdno_burgers_generate_desc
+    _fields_ = [(k, I) for k in ('N', 's', 't', 'steps', 'record_time', 'f_time', 'num_t', 'st', 'sx', 'f_rows', 'cols', 'waves', 'points',
+                                 'clamp')] + [(k, F) for k in ('c', 'd', 'dm', 'dt', 'alpha')]
+
+
 class BurgersGuidanceDesc(C.Structure):     # include/wdno_hip.h: wdno_burgers_guidance_desc
     _fields_ = [(k, I) for k in ('B', 'C', 'H', 'W', 'sample_stride', 'chan_stride', 'row_stride', 'h', 'w', 'n_t', 'n_x', 'L', 'mode', 'ntile',
                                  'tw', 'lds_bytes', 'num_timesteps', 'condition_f', 'clip_x0')] + [(k, F) for k in ('wu', 'wf')]
@@ -196,6 +201,7 @@ PROTOTYPES = {
     'wdno_relpos_bias_fwd': (I, [P, P, P, I, I, P]),
     'wdno_relpos_bias_bwd': (I, [P, P, P, I, I, I, P]),
     'wdno_burgers_solve': (I, [P, P, P, C.POINTER(BurgersDesc), P]),
+    'wdno_burgers_generate': (I, [P, P, P, P, P, C.POINTER(BurgersGenerateDesc), P]),
     'wdno_burgers_guidance': (I, [P, P, P, P, P, P, P, P, P, C.POINTER(BurgersGuidanceDesc), PF, P]),
     'wdno_smoke_solve': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeSolveDesc), P]),
     'wdno_smoke_generate': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeGenerateDesc), P]),

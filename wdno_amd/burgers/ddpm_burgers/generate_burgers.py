@@ -2,8 +2,10 @@
 control (eval_ddpm_burgers.py:203, test_util.py:75,77), runs as one HIP launch (wdno_amd.burgers_solver, csrc/burgers.hip).
 
 Same signature and defaults as the reference; `mode` is unused there and here. Every other name (make_data_varying_f,
-generate_data_burgers_equation, Diff_mat_1D, VISC, ...) comes from the reference's module when that is on sys.path behind this tree. The
-data-generation script itself still runs the reference's module (as a script its globals are the reference's own)."""
+generate_data_burgers_equation, Diff_mat_1D, VISC, ...) comes from the reference's module when that is on sys.path behind this tree.
+
+Run as a script it is the data-set generator with the reference script's arguments: wdno_amd.burgers_datagen, one HIP launch per batch of
+800 trajectories (csrc/burgers_datagen.hip), writing the train / test files data_burgers_1d.py and wave_trans.py read."""
 import wdno_amd
 from wdno_amd import burgers_solver as _solver
 
@@ -18,3 +20,8 @@ def burgers_numeric_solve_free(u0, f, visc, T, num_t=80, dt=1/76800, s=120*16, m
 
 def __getattr__(name):          # make_data_varying_f, generate_data_burgers_equation, Diff_mat_1D, VISC, ... from the reference module
     return _reference_getattr(name)
+
+
+if __name__ == '__main__':
+    from wdno_amd import burgers_datagen as _datagen
+    _datagen.main()

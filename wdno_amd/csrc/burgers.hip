@@ -16,7 +16,9 @@
 // Forcing. f [N][Nt_f][nxf] is interpolated to s points inside the kernel (torch's linear, align_corners = False: src = max((i + 0.5) nxf / s
 // - 0.5, 0)), once per control interval; the coarse values of the next interval are loaded while the current one runs. u0 likewise.
 // Records go straight into out [N][num_t + 1][out_cols] (only the columns g % sub_s == 0).
-#include "common.h"
+//
+// The step itself (point update, halo, record rule) is in burgers_step.h, shared with burgers_datagen.hip.
+#include "burgers_step.h"
 
 namespace {
 
@@ -40,49 +42,14 @@ __device__ __forceinline__ float bg_mix(float x0, float x1, float lam) {
   return __fadd_rn(__fmul_rn(x0, __fadd_rn(1.f, -lam)), __fmul_rn(x1, lam));
 }
 
-// one point: a = u[i-1], b = u[i], e = u[i+1], fv = f[f_idx][i]
-__device__ __forceinline__ float bg_update(float a, float b, float e, float fv, const BurgersP& p) {
-  const float tr = __fadd_rn(__fmul_rn(__fmul_rn(a, a), p.h), __fmul_rn(__fmul_rn(e, e), -p.h));              // -(1/2) transport
-  const float df = __fadd_rn(__fadd_rn(__fmul_rn(a, p.d), __fmul_rn(b, p.dm)), __fmul_rn(e, p.d));             // diffusion
-  return __fadd_rn(b, __fmul_rn(p.dt, __fadd_rn(__fadd_rn(tr, df), fv)));
-}
-
-// DPP wave shifts (wave_shr:1 / wave_shl:1): the value of lane l - 1 / l + 1, 0 where there is none
-__device__ __forceinline__ float bg_from_prev_lane(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float bg_from_next_lane(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-
-// g0 as a value the compiler cannot see through: keeps the per-point index arithmetic of the rare paths (records, interval changes) from being
-// hoisted out of the step loop into registers (3-4 per point otherwise: 118 VGPRs at P = 8 instead of ~50)
-__device__ __forceinline__ int bg_opaque(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-template <int P>
-__device__ __forceinline__ void bg_record(const float (&u)[P], int g0, float* __restrict__ row, const BurgersP& p) {
-#pragma unroll
-  for (int k = 0; k < P; ++k) {
-    const int g = bg_opaque(g0) + k;
-    if (g < p.s && g % p.sub_s == 0) row[g / p.sub_s] = u[k];
-  }
-}
-
 template <int W, int P>
 __global__ __launch_bounds__(W * 64) void burgers_solve_kernel(BurgersP p) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: scalar branches below
   const int g0 = (w * 64 + lane) * P;
   const bool wave_full = (w + 1) * 64 * P <= p.s;        // no point of this wave is past the grid: nothing to re-zero
   const size_t n = blockIdx.x;
-  // halo[par][0][w + 1] = last point of wave w, halo[par][1][w] = first point of wave w; halo[.][0][0] and halo[.][1][W] stay 0 (the ghosts)
   __shared__ float halo[2][2][W + 1];
-  if (W > 1) {
-    if (threadIdx.x < 4 * (W + 1)) (&halo[0][0][0])[threadIdx.x] = 0.f;
-    __syncthreads();
-  }
+  bg_halo_init<W>(halo);
 
   float u[P], fc[P], x0n[P], x1n[P];
   const float* __restrict__ u0 = p.u0 + n * p.nx0;
@@ -119,32 +86,7 @@ __global__ __launch_bounds__(W * 64) void burgers_solve_kernel(BurgersP p) {
     }
     const int j_end = min(p.steps, (iv + 1) * p.f_time);
     for (int j = iv * p.f_time; j < j_end; ++j) {
-      float nu[P];
-      if (W > 1) {
-        if (lane == 0) halo[par][1][w] = u[0];
-        if (lane == 63) halo[par][0][w + 1] = u[P - 1];
-      }
-      const float from_prev = bg_from_prev_lane(u[P - 1]), from_next = bg_from_next_lane(u[0]);
-#pragma unroll
-      for (int k = 1; k < P - 1; ++k) nu[k] = bg_update(u[k - 1], u[k], u[k + 1], fc[k], p);
-      float left = from_prev, right = from_next;
-      if (W > 1) {
-        __syncthreads();
-        const float hl = halo[par][0][w], hr = halo[par][1][w + 1];
-        left = lane == 0 ? hl : left;
-        right = lane == 63 ? hr : right;
-        par ^= 1;
-      }
-      nu[0] = bg_update(left, u[0], u[1], fc[0], p);
-      nu[P - 1] = bg_update(u[P - 2], u[P - 1], right, fc[P - 1], p);
-      if (wave_full) {
-#pragma unroll
-        for (int k = 0; k < P; ++k) u[k] = nu[k];
-      } else {
-        const int gq = bg_opaque(g0);
-#pragma unroll
-        for (int k = 0; k < P; ++k) u[k] = gq + k < p.s ? nu[k] : 0.f;
-      }
+      BG_STEP();
       if (--rec_left == 0) {
         bg_record<P>(u, g0, out + (size_t)row * p.out_cols, p);
         ++row;
