@@ -273,7 +273,9 @@ def test_act16_conv_output_is_the_rounded_fp32_output(ops):
     ops.ACT16 = False
 
 
-@pytest.mark.parametrize('shape,groups', [((2, 6, 20, 20, 64), 8), ((3, 16, 16, 128), 1), ((2, 4, 8, 8, 24), 4)])
+@pytest.mark.parametrize('shape,groups', [((2, 6, 20, 20, 64), 8), ((3, 16, 16, 128), 1), ((2, 4, 8, 8, 24), 4),
+                                          # row counts that are no multiple of the eight rows a row group loads per round, over several chunks
+                                          ((2, 515, 256), 1), ((1, 4100, 32), 8), ((2, 70, 512), 128)])
 def test_act16_groupnorm_reads_bf16_storage_exactly(ops, shape, groups):
     """GroupNorm on a bf16-stored activation == GroupNorm on the same values stored as fp32, bit for bit, in every form the U-Nets use: fp32
     output, planes output, + residual; and backward (dx planes, column sums, parameter gradients) with dy stored as fp32 and as bf16."""
