@@ -656,6 +656,51 @@ int wdno_burgers_guidance(const float* x_t, const float* in, const int64_t* t, c
                           const float* rescaler, const float* target, float* out, const wdno_burgers_guidance_desc* d, const float* filt,
                           wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ smoke control-objective guidance
+ * The gradient of the control objective of the smoke inference (smoke/inference_2d.py:30-66) in closed form, at most two launches. For a
+ * network-unit tensor x [B][F][C][H][W] (C >= 42), coefficient block (tc, hc, wc) and field size (to, ho, wo):
+ *   xs    = x RESCALER;  channel 8 f + band of frames < tc, rows < hc, columns < wc = sub-band band = 4 bt + 2 bh + bw of field f (f < 5)
+ *   state = IDWT3(xs)[:, :, :to, :ho, :wo]      (W pass, H pass, T pass; zero mode, L = 6: an axis of v coefficients gives 2 v - 4 samples)
+ *   lo, hi = the means of xs[:, k < tc, C - 1] over rows < half and rows >= half;  smoke_out = IDWT1(lo, hi)
+ *   J = w_init sum_b mean((state[b, 0, 0] - init_u[b])^2)
+ *       + (1 - is_condition_control) (w_energy sum_b mean(state[b, 3:5]^2) - sum_b smoke_out[b, to - 1])
+ * J is quadratic in the state and linear in the smoke-out channel, so with the residual r (2 w_init (state - init_u) / (ho wo) on frame 0 of
+ * field 0 when has_init_u and w_init != 0; 2 w_energy state / (2 to ho wo) on fields 3 and 4 when not is_condition_control and
+ * w_energy != 0; 0 elsewhere on the reconstruction grid)
+ *   g = dJ/dxs = IDWT3^T(r) on [:, :tc, 0:40, :hc, :wc]   (exactly 0 for fields 1, 2 and, for field 0, on coefficient frames >= 3)
+ *   g[:, k < tc, C - 1, rows < half] = -succ[0][k] / (half W),  g[:, k < tc, C - 1, rows >= half] = -succ[1][k] / ((H - half) W)
+ *       (not is_condition_control; succ [2][tc] = d smoke_out[to - 1] / d(lo, hi), two constant vectors the caller computes once)
+ * and exactly 0 everywhere else. g is NOT multiplied by RESCALER: the reference differentiates with respect to xs.
+ *   x_t != NULL (fused mode, one sampling step, diffusion_2d.py:723-754): in = eps, x0 = c1[t_b] x_t - c2[t_b] eps (clamped to [-1, 1]
+ *     when clip_x0), out = eps + g(x0) s_table[t_b] -- a product then a sum, two roundings; out = eps bit for bit wherever g is 0.
+ *     t_b is clamped into [0, num_timesteps).
+ *   x_t == NULL (gradient mode): in = x0, out = g; t, c1, c2, s_table are not read.
+ * rescaler [C]; init_u [B][ho][wo] or NULL; filt: host pointer to (dec_lo, dec_hi, rec_lo, rec_hi), L taps each, as wdno_dwt_*.
+ * Launch 1 (skipped when r is 0 everywhere): a workgroup per (sample, field, tile of tn reconstruction frames x hn rows) synthesises fields
+ * 3 and 4 in full and frame 0 of field 0 from the coefficients, read in place in the packed state with x0 RESCALER formed on the fly, and
+ * writes r, scaled and cropped, to ws: B (2 to ho wo + ho wo) floats (wdno_smoke_guidance_ws_bytes; 0 for a descriptor that is refused).
+ * Launch 2: a workgroup per (sample, field, tile of kt coefficient frames x kh rows) turns r into g and writes `out` there; these and
+ * ncopy further workgroups per sample share the rest of the tensor (the copy of eps, or zeros, and the smoke-out term). Every intermediate
+ * of a tile lives in lds1_bytes / lds2_bytes of LDS. Nothing is allocated; no atomics, every sum in a fixed order: a sample's result does
+ * not depend on B or its index. `in` and `out` must not overlap. tn, hn even; lds*_bytes <= 64 KiB and what the layout needs
+ * (wdno_amd/smoke/guidance.py: plan). WDNO_EUNSUPPORTED for anything but mode 1 (zero) with L = 6 (bior1.3); WDNO_EINVAL for inconsistent
+ * integers: a block larger than the tensor, a crop larger than the reconstruction, tiles or LDS sizes that do not fit. */
+typedef struct {
+  int B, F, C, H, W;                                            /* the tensors x_t, in, out */
+  int sample_stride, frame_stride, chan_stride, row_stride;     /* in elements; columns are contiguous */
+  int tc, hc, wc, to, ho, wo;                                   /* coefficient block (shape) and field size (ori_shape): to <= 2 tc - 4, ... */
+  int L, mode, half;
+  int num_timesteps;                                            /* length of c1, c2, s_table */
+  int clip_x0, is_condition_control, has_init_u;
+  int tn, hn, kt, kh, ncopy;
+  int lds1_bytes, lds2_bytes;
+  float w_energy, w_init;
+} wdno_smoke_guidance_desc;
+size_t wdno_smoke_guidance_ws_bytes(const wdno_smoke_guidance_desc* d);
+int wdno_smoke_guidance(const float* x_t, const float* in, const int64_t* t, const float* c1, const float* c2, const float* s_table,
+                        const float* rescaler, const float* init_u, const float* succ, float* out, void* ws, size_t ws_bytes,
+                        const wdno_smoke_guidance_desc* d, const float* filt, wdno_stream_t s);
+
 /* ------------------------------------------------------------------------------------------------ smoke control-evaluation solver
  * solver() of smoke/dataset/evaluate_solver.py:135-196 for B simulations in one launch, one workgroup of `threads` (1024 or 512) threads per
  * simulation: num_t (<= 256) frames of { velocity = interior of the previous frame's + 16-cell rim of the control (c1, c2 [B][nt][nx][nx],

@@ -62,6 +62,12 @@ class BurgersGuidanceDesc(C.Structure):     # include/wdno_hip.h: wdno_burgers_g
                                  'tw', 'lds_bytes', 'num_timesteps', 'condition_f', 'clip_x0')] + [(k, F) for k in ('wu', 'wf')]
 
 
+class SmokeGuidanceDesc(C.Structure):       # include/wdno_hip.h: wdno_smoke_guidance_desc
+    _fields_ = [(k, I) for k in ('B', 'F', 'C', 'H', 'W', 'sample_stride', 'frame_stride', 'chan_stride', 'row_stride', 'tc', 'hc', 'wc', 'to', 'ho',
+                                 'wo', 'L', 'mode', 'half', 'num_timesteps', 'clip_x0', 'is_condition_control', 'has_init_u', 'tn', 'hn', 'kt', 'kh',
+                                 'ncopy', 'lds1_bytes', 'lds2_bytes')] + [(k, F) for k in ('w_energy', 'w_init')]
+
+
 class SmokeSolveDesc(C.Structure):          # include/wdno_hip.h: wdno_smoke_solve_desc
     _fields_ = [(k, I) for k in ('B', 'nt', 'nx', 'time_interval', 'space_interval', 'num_t', 'max_iter', 'n_out', 'threads')] + [('accuracy', F)]
 
@@ -203,6 +209,8 @@ PROTOTYPES = {
     'wdno_burgers_solve': (I, [P, P, P, C.POINTER(BurgersDesc), P]),
     'wdno_burgers_generate': (I, [P, P, P, P, P, C.POINTER(BurgersGenerateDesc), P]),
     'wdno_burgers_guidance': (I, [P, P, P, P, P, P, P, P, P, C.POINTER(BurgersGuidanceDesc), PF, P]),
+    'wdno_smoke_guidance_ws_bytes': (Z, [C.POINTER(SmokeGuidanceDesc)]),
+    'wdno_smoke_guidance': (I, [P, P, P, P, P, P, P, P, P, P, P, Z, C.POINTER(SmokeGuidanceDesc), PF, P]),
     'wdno_smoke_solve': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeSolveDesc), P]),
     'wdno_smoke_generate': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeGenerateDesc), P]),
     'wdno_smoke_noise': (I, [P, P, P, P, I, C.c_uint64, P, P]),

@@ -343,9 +343,11 @@ def guided_sampling_loop_burgers(mod, x, src, desc, guidance, s_table, *, ddim_p
     return sampling_loop(mod, x, src, desc, ddim_pairs=ddim_pairs, eta=eta, cond_first=True, use_graph=use_graph, guidance=guidance, s_table=s_table)
 
 
-def sampling_loop(mod, x, src, desc, *, ddim_pairs=None, eta=0.0, cond_first, use_graph=None, guidance=None, s_table=None):
+def sampling_loop(mod, x, src, desc, *, ddim_pairs=None, eta=0.0, cond_first, use_graph=None, guidance=None, s_table=None, guidance_key=None):
     """The sampling loop of both GaussianDiffusion classes (diffusion_1d.py:310-460, diffusion_2d.py:788-933): unguided, or (guidance, s_table
-    given, Burgers order only) with the noise estimate of every step passed through guidance.guide -- see guided_sampling_loop_burgers.
+    given) with the noise estimate of every step passed through guidance.guide -- see guided_sampling_loop_burgers; in the smoke order
+    (smoke/guidance.py: SmokeGuidance, diffusion_2d.py:723-754) the step is U-Net -> guide -> the fused update -> conditions.
+    guidance_key: what else the caller wants in the captured step's cache key.
 
     x: the initial draw [B, ...]; src / desc: clean values and predicate of the conditioned positions. cond_first = True is the
     Burgers order (conditions imposed before every U-Net call; the caller imposes them once more on the result), False the
@@ -366,7 +368,6 @@ def sampling_loop(mod, x, src, desc, *, ddim_pairs=None, eta=0.0, cond_first, us
         use_graph = SAMPLE_GRAPH and sum(noisy) >= SAMPLE_GRAPH_MIN_STEPS
     sg, gkw, s_dev = None, {}, None
     if guidance is not None:
-        assert cond_first, 'guidance launches are part of the Burgers step order only'
         s_dev = s_table.to(dev, torch.float32).contiguous()
 
         def guided_factory(static):
@@ -375,7 +376,8 @@ def sampling_loop(mod, x, src, desc, *, ddim_pairs=None, eta=0.0, cond_first, us
                 eps = guidance.guide(mod, xx, mod.model(xx, t, None), t, static['s_table'], ddim)
                 return (ddim_update_dev(mod, xx, eps, noise, t, coef) if ddim else p_sample_update(mod, xx, eps, noise, t, clamp=True))[0]
             return guided
-        gkw = dict(guided_factory=guided_factory, guided_key=('burgers-guided', id(guidance), guidance.key()), static=dict(s_table=s_dev),
+        gkw = dict(guided_factory=guided_factory, guided_key=('burgers-guided' if cond_first else 'smoke-guided', id(guidance), guidance.key(), guidance_key),
+                   static=dict(s_table=s_dev),
                    keep=guidance)
     if use_graph and any(noisy):
         sg = _step_graph(mod, shape, desc, ddim, cond_first, dev, **gkw)

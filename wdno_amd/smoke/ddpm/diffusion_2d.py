@@ -238,6 +238,21 @@ class GaussianDiffusion(nn.Module):
         pred = mean if noise is None else mean + (0.5 * logvar).exp() * noise
         return pred, x_start
 
+    def guidance_s_table(self, design_guidance):
+        """The guidance step size of every timestep, [num_timesteps] fp32: what model_predictions multiplies the design gradient with."""
+        if design_guidance == 'standard':
+            return torch.full((self.num_timesteps,), self.standard_fixed_ratio, dtype=torch.float32)
+        if design_guidance == 'standard-alpha':
+            return (self.coeff_ratio * self.betas.flip(0)).float()
+        raise ValueError(design_guidance)
+
+    def _fused_guided_loop(self, x, src, desc, design_fn, design_guidance, init_u, **kw):
+        """A design_fn with `fused_step` (smoke/guidance.py: SmokeGuidance): every step is U-Net -> design_fn.guide -> the fused update."""
+        design_fn.set_init_u(init_u, x.device)      # the buffer lives on the sampling device from the first call: its address is in the graph key
+        gkey = (design_guidance, float(self.standard_fixed_ratio), float(self.coeff_ratio))
+        return K.sampling_loop(self, x, src, desc, cond_first=False, use_graph=self.use_graph, guidance=design_fn,
+                               s_table=self.guidance_s_table(design_guidance), guidance_key=gkey, **kw)
+
     def _condition_source(self, shape, device, init, control, low):
         """Clean values for every conditioned position, assembled once per sampling call."""
         src = torch.zeros(shape, device=device, dtype=torch.float32)
@@ -259,6 +274,8 @@ class GaussianDiffusion(nn.Module):
         x = K.apply_cond(self.sample_noise(list(shape), device).contiguous(), src, desc)
         if design_fn is None and not self.self_condition:          # unguided: fused launches, the step replayed from one HIP graph
             return K.sampling_loop(self, x, src, desc, cond_first=False, use_graph=self.use_graph)
+        if getattr(design_fn, 'fused_step', False) and not self.self_condition:
+            return self._fused_guided_loop(x, src, desc, design_fn, design_guidance, init_u)
         if getattr(design_fn, 'graph_safe', False) and not self.self_condition:
             return K.guided_sampling_loop_smoke(self, x, src, desc, design_fn, design_guidance, low=low, init=init, init_u=init_u, use_graph=self.use_graph)
         x_start = None
@@ -280,6 +297,8 @@ class GaussianDiffusion(nn.Module):
         pairs = K.ddim_time_pairs(self.num_timesteps, self.sampling_timesteps)
         if design_fn is None and not self.self_condition:
             return K.sampling_loop(self, img, src, desc, ddim_pairs=pairs, eta=eta, cond_first=False, use_graph=self.use_graph)
+        if getattr(design_fn, 'fused_step', False) and not self.self_condition:
+            return self._fused_guided_loop(img, src, desc, design_fn, design_guidance, init_u, ddim_pairs=pairs, eta=eta)
         if getattr(design_fn, 'graph_safe', False) and not self.self_condition:
             return K.guided_sampling_loop_smoke(self, img, src, desc, design_fn, design_guidance, ddim_pairs=pairs, eta=eta, low=low, init=init,
                                                 init_u=init_u, use_graph=self.use_graph)

@@ -6,7 +6,21 @@ The sampler calls `design_fn(x)` once per step (diffusion_2d.py:733-741); the re
 (the first two terms drop out when the model is conditioned on the control) and returns dJ/dx'. Here the same expression is
 written on the HIP transforms, whose backward passes are the exact adjoint kernels (wdno_dwt_inv_adjoint), so the gradient
 costs one synthesis and one adjoint-synthesis launch triple per call.
+
+SmokeGuidance      -- the same gradient from csrc/smoke_guidance.hip (include/wdno_hip.h: wdno_smoke_guidance): two launches, no unpack copy, only
+                      the part of the state J reads is synthesised. `fused_step = True` lets GaussianDiffusion.sample run every guided step as
+                      U-Net -> guide() -> the fused update of the unguided loop (diffusion_core.sampling_loop); guide() predicts x0 from
+                      (x_t, eps) and returns eps + g(x0) s[t].
+plan()             -- pure Python: the descriptor's integers, tiles, LDS and workspace bytes; needs neither the library nor a GPU.
+
+Tile rule. Launch 1 tiles the reconstruction by (tn frames, hn rows), launch 2 the coefficient block by (kt frames, kh rows), both full
+width. A synthesis tile stages tn/2 + 2 coefficient frames and hn/2 + 2 rows (halo: 2 per side per axis), an adjoint tile reads 2 kt + 4
+residual frames and 2 kh + 4 rows, so small tiles repeat work; the first pair of TILES1 and of TILES2 whose buffers fit 64 KiB of LDS is taken
+(the 40 x 40 state with a 34 x 34 block: (tn, hn) = (4, 8) at 47 488 B = 46.4 KiB and (kt, kh) = (2, 4) at 20 480 B = 20 KiB; on the
+80 x 80 super-resolution state the synthesis tile falls back to (4, 4), the adjoint tile stays at (2, 4)).
 """
+import ctypes as C
+
 import torch
 
 from wdno_amd import wavelets as W
@@ -100,6 +114,176 @@ def guidance_fn_explicit(x, shape, ori_shape, rescaler, wave_type='bior1.3', pad
         g[:, :tc, -1, :half, :] -= (g_lo / (half * ww)).reshape(1, tc, 1, 1)
         g[:, :tc, -1, half:, :] -= (g_hi / ((hh - half) * ww)).reshape(1, tc, 1, 1)
     return g
+
+
+# ----------------------------------------------------------------------------------------------------- the guidance kernel
+LDS_BUDGET = 64 * 1024          # what a launch may ask for without opting into the large-LDS mode
+SUPPORTED = {('bior1.3', 'zero')}                 # the (L, mode) instance csrc/smoke_guidance.hip is built for
+TILES1 = ((4, 8), (4, 4), (2, 4), (2, 2))         # (tn, hn) of the synthesis launch, in order of preference
+TILES2 = ((2, 4), (2, 2), (1, 2), (1, 1))         # (kt, kh) of the adjoint launch
+NCOPY = 32                                        # workgroups per sample that only take part in the shared copy
+
+
+def lds1_bytes(wc, wo, tn, hn):
+    """LDS of a synthesis workgroup: a staged band pair [2][KT][KH][wc], the W pass [4][KT][KH][wo], the H pass [2][KT][hn][wo]."""
+    kt, kh = tn // 2 + 2, hn // 2 + 2
+    return 4 * (2 * kt * kh * wc + 4 * kt * kh * wo + 2 * kt * hn * wo)
+
+
+def lds2_bytes(wo, kt, kh):
+    """LDS of an adjoint workgroup: the T pass [2][kt][2 kh + 4][wo] and the H pass [4][kt][kh][wo]."""
+    return 4 * (2 * kt * (2 * kh + 4) * wo + 4 * kt * kh * wo)
+
+
+def plan(x_shape, shape, ori_shape, wave_type='bior1.3', pad_mode='zero', is_condition_control=False):
+    """Host integers of one wdno_smoke_guidance call on a contiguous x of x_shape = (B, F, C, H, W). ValueError for a (wave, mode) the kernel
+    is not built for, a block larger than the tensor, a crop larger than the reconstruction, and tiles that do not fit the LDS budget."""
+    from wdno_amd.filters import filter_bank
+    if (wave_type, pad_mode) not in SUPPORTED:
+        raise ValueError(f'smoke guidance kernel: (wave, mode) = ({wave_type!r}, {pad_mode!r}) is not built; supported: {sorted(SUPPORTED)}')
+    L = len(filter_bank(wave_type)[2])
+    B, F, Cc, H, W = (int(v) for v in x_shape)
+    tc, hc, wc = (int(v) for v in shape)
+    to, ho, wo = (int(v) for v in ori_shape)
+    if Cc < 42:
+        raise ValueError(f'smoke guidance: {Cc} channels; 40 coefficient channels and the two condition channels are needed')
+    if not (3 <= tc <= F and 3 <= hc <= H and 3 <= wc <= W):
+        raise ValueError(f'smoke guidance: coefficient block {(tc, hc, wc)} does not fit the {(F, H, W)} tensor or is shorter than the filter')
+    rec = tuple(2 * v - L + 2 for v in (tc, hc, wc))
+    if not all(1 <= o <= r for o, r in zip((to, ho, wo), rec)):
+        raise ValueError(f'smoke guidance: field {(to, ho, wo)} is not a crop of the {rec} reconstruction')
+    if B < 1 or B > 65535 or F * Cc * H * W >= 2 ** 31 or H < 2:
+        raise ValueError(f'smoke guidance: tensor {tuple(x_shape)} is outside the kernel\'s 32-bit strides / grid')
+    ev = lambda v: v + (v & 1)
+    t1 = [(min(tn, ev(to)), min(hn, ev(ho))) for tn, hn in TILES1]
+    t1 = [t for t in t1 if lds1_bytes(wc, wo, *t) <= LDS_BUDGET]
+    t2 = [(min(kt, tc), min(kh, hc)) for kt, kh in TILES2]
+    t2 = [t for t in t2 if lds2_bytes(wo, *t) <= LDS_BUDGET]
+    if not t1 or not t2:
+        raise ValueError(f'smoke guidance: the smallest tile of a {(tc, hc, wc)} block with {wo} columns does not fit {LDS_BUDGET} B of LDS')
+    (tn, hn), (kt, kh) = t1[0], t2[0]
+    return dict(B=B, F=F, C=Cc, H=H, W=W, sample_stride=F * Cc * H * W, frame_stride=Cc * H * W, chan_stride=H * W, row_stride=W,
+                tc=tc, hc=hc, wc=wc, to=to, ho=ho, wo=wo, L=L, mode=1, half=_split_row(H), is_condition_control=int(bool(is_condition_control)),
+                tn=tn, hn=hn, kt=kt, kh=kh, ncopy=NCOPY, lds1_bytes=lds1_bytes(wc, wo, tn, hn), lds2_bytes=lds2_bytes(wo, kt, kh),
+                ws_bytes=4 * B * (2 * to * ho * wo + ho * wo))
+
+
+class SmokeGuidance:
+    """`design_fn` for GaussianDiffusion.sample on the guidance kernel: `g(x, init_u=...)` returns dJ/d(x RESCALER) like GuidanceFn does, from
+    two launches. `graph_safe` and `fused_step` tell the sampler that the guided step is U-Net -> guide() -> the fused update, captured like
+    the unguided one; both are False when the kernel does not take the configuration (plan() raises), and the object then answers through
+    guidance_fn_explicit.
+
+    The initial density of the fused route lives in one device buffer per (device, shape), kept for the object's lifetime:
+    set_init_u(init_u, device) refills it IN PLACE, so a captured sampling step is replayed on the next batch's initial density, and
+    set_init_u(None) only switches the term off. The workspaces belong to the object, one per (device, tensor shape), and are never
+    replaced or freed while the object lives: a captured step of one batch size keeps a valid pointer whatever else the object is called on."""
+
+    def __init__(self, shape, ori_shape, rescaler, is_condition_control=False, w_energy=0.0, w_init=0.0, wave_type='bior1.3', pad_mode='zero'):
+        self.shape, self.ori_shape = tuple(int(v) for v in shape), tuple(int(v) for v in ori_shape)
+        self.is_condition_control, self.w_energy, self.w_init = bool(is_condition_control), float(w_energy), float(w_init)
+        self.wave_type, self.pad_mode = wave_type, pad_mode
+        self.rescaler = torch.as_tensor(rescaler, dtype=torch.float32)
+        self.init_u = None                    # the buffer guide() reads, or None: no initial-density term
+        self._u_bufs = {}                     # (device, shape) -> buffer
+        self._resc, self._succ, self._ws, self._desc = {}, {}, {}, {}
+        try:
+            tc, hc, wc = self.shape
+            plan((1, tc, max(42, self.rescaler.numel()), hc, wc), self.shape, self.ori_shape, wave_type, pad_mode, is_condition_control)
+            self.graph_safe = self.fused_step = True
+        except ValueError:
+            self.graph_safe = self.fused_step = False
+
+    def key(self):
+        """What a captured launch of this object bakes in besides its workspace (fixed per device and tensor shape, which the step graph's
+        key carries): the constants and the density buffer."""
+        return (self.shape, self.ori_shape, self.is_condition_control, self.w_energy, self.w_init, self.wave_type, self.pad_mode,
+                None if self.init_u is None else (tuple(self.init_u.shape), str(self.init_u.device), self.init_u.data_ptr()))
+
+    def set_init_u(self, init_u, device=None):
+        """The initial density [B, ho, wo] of the fused route, copied into the object's buffer on `device` (default: init_u's own)."""
+        if init_u is None:
+            self.init_u = None
+            return self
+        to, ho, wo = self.ori_shape
+        u = torch.as_tensor(init_u).detach().reshape(-1, ho, wo)
+        dev = torch.device(device) if device is not None else u.device
+        if dev.type == 'cuda' and dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        k = (str(dev), tuple(u.shape))
+        buf = self._u_bufs.get(k)
+        if buf is None:
+            buf = self._u_bufs[k] = torch.empty(tuple(u.shape), dtype=torch.float32, device=dev)
+        buf.copy_(u)                          # same storage on every call: captured launches read the new density
+        self.init_u = buf
+        return self
+
+    # ------------------------------------------------------------------ launches
+    def _launch(self, x_t, inp, t, c1, c2, s_table, clip_x0, init_u):
+        from wdno_amd import _lib
+        from wdno_amd.filters import filter_bank
+        from wdno_amd.ops import _chk, _p, _stream
+        inp = _chk(inp, 'x')
+        dev = inp.device
+        if inp.dim() != 5:
+            raise ValueError(f'SmokeGuidance: x must be [B, F, C, H, W], got {tuple(inp.shape)}')
+        if x_t is not None:                   # fused mode: everything the launch indexes is checked here, a mismatch would read out of bounds
+            nT = int(s_table.numel())
+            if tuple(x_t.shape) != tuple(inp.shape) or x_t.device != dev:
+                raise ValueError(f'SmokeGuidance.guide: x_t {tuple(x_t.shape)} on {x_t.device} against eps {tuple(inp.shape)} on {dev}')
+            if t.dtype != torch.int64 or tuple(t.shape) != (inp.shape[0],) or t.device != dev or not t.is_contiguous():
+                raise ValueError(f'SmokeGuidance.guide: t must be a contiguous int64 [{inp.shape[0]}] on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}')
+            for name, tab in (('s_table', s_table), ('sqrt_recip_alphas_cumprod', c1), ('sqrt_recipm1_alphas_cumprod', c2)):
+                if tab.dtype != torch.float32 or tab.device != dev or tab.dim() != 1 or not tab.is_contiguous() or tab.numel() < nT or nT < 1:
+                    raise ValueError(f'SmokeGuidance.guide: {name} must be a contiguous fp32 table of at least {nT} entries on {dev}, '
+                                     f'got {tab.dtype} {tuple(tab.shape)} on {tab.device}')
+        if init_u is not None:
+            if init_u.device != dev or init_u.dtype != torch.float32 or not init_u.is_contiguous():
+                init_u = init_u.to(dev, torch.float32).contiguous()
+            if init_u.numel() != inp.shape[0] * self.ori_shape[1] * self.ori_shape[2]:
+                raise ValueError(f'SmokeGuidance: init_u {tuple(init_u.shape)} against batch {inp.shape[0]} of fields {self.ori_shape[1:]}')
+        key = (tuple(inp.shape), bool(clip_x0), 0 if s_table is None else int(s_table.numel()), init_u is not None)
+        d = self._desc.get(key)
+        if d is None:
+            pl = plan(tuple(inp.shape), self.shape, self.ori_shape, self.wave_type, self.pad_mode, self.is_condition_control)
+            nws = pl.pop('ws_bytes')
+            desc = _lib.SmokeGuidanceDesc(**pl, num_timesteps=key[2], clip_x0=int(bool(clip_x0)), has_init_u=int(init_u is not None),
+                                          w_energy=self.w_energy, w_init=self.w_init)
+            filt = [float(v) for bank in filter_bank(self.wave_type) for v in bank]
+            d = self._desc[key] = (desc, (C.c_float * len(filt))(*filt), nws)
+        r = self._resc.get(dev)
+        if r is None:
+            r = self._resc[dev] = self.rescaler.reshape(-1).to(dev).contiguous()
+        if r.numel() != inp.shape[2]:
+            raise ValueError(f'SmokeGuidance: RESCALER has {r.numel()} channels, x has {inp.shape[2]}')
+        succ = None
+        if not self.is_condition_control:
+            succ = self._succ.get(dev)
+            if succ is None:
+                succ = self._succ[dev] = torch.stack(_success_gradient(self.shape[0], self.ori_shape[0], self.wave_type, self.pad_mode, dev)).contiguous()
+        wkey = (dev, tuple(inp.shape))        # one workspace per tensor shape, never replaced: a captured step holds its raw address
+        ws = self._ws.get(wkey)
+        if ws is None:
+            ws = self._ws[wkey] = torch.empty(max(d[2], 16), dtype=torch.uint8, device=dev)
+        out = torch.empty_like(inp)
+        _lib.check(_lib.load().wdno_smoke_guidance(_p(x_t), _p(inp), _p(t), _p(c1), _p(c2), _p(s_table), _p(r), _p(init_u), _p(succ), _p(out),
+                                                   _p(ws), ws.numel(), C.byref(d[0]), d[1], _stream()), 'wdno_smoke_guidance')
+        return out
+
+    def __call__(self, x, low=None, init=None, init_u=None):
+        """dJ/d(x RESCALER) (gradient mode); low and init are ignored, as the reference's objective ignores them."""
+        if not self.graph_safe:
+            return guidance_fn_explicit(x, self.shape, self.ori_shape, self.rescaler.to(x.device), self.wave_type, self.pad_mode,
+                                        self.is_condition_control, self.w_energy, self.w_init, init_u)
+        return self._launch(None, x.detach(), None, None, None, None, False, init_u)
+
+    def guide(self, mod, x_t, eps, t, s_table, clip_x0):
+        """One sampling step's guidance (fused mode): eps + g(x0) s_table[t] with x0 = c1[t] x_t - c2[t] eps (clamped when clip_x0), the schedule
+        tables of the diffusion module `mod`, t a device int64 [B] and the initial density of set_init_u."""
+        from wdno_amd.ops import _chk
+        if self.init_u is not None and self.init_u.device != eps.device:
+            self.set_init_u(self.init_u, eps.device)
+        return self._launch(_chk(x_t, 'x_t'), eps, t, mod.sqrt_recip_alphas_cumprod, mod.sqrt_recipm1_alphas_cumprod, s_table, clip_x0, self.init_u)
 
 
 class GuidanceFn:
