@@ -753,6 +753,47 @@ int wdno_smoke_generate(const int* scene_i, const float* scene_v, const long lon
 int wdno_smoke_noise(const long long* scene_index, const int* frame, const int* is_kick, const float* kick_v, int n,
                      unsigned long long seed, float* out, wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ smoke inference: reconstruction and scoring
+ * wdno_smoke_reconstruct: the wavelet branch of InferencePipeline.run_base_model (smoke/inference_2d.py:137-152) for the whole batch in one
+ * launch. For the sampled state x [B][F][C][H][W] in network units (C >= 42, strides in elements, columns contiguous), rescaler [C], the
+ * coefficient block (tc, hc, wc) and the field size (to, ho, wo), with xs = x RESCALER formed on the fly and the coefficients read in place
+ * (channel 8 f + band of frames < tc, rows < hc, columns < wc = sub-band band = 4 bt + 2 bh + bw of field f):
+ *   pred[b, :, f]  = IDWT3(xs)[f][:to, :ho, :wo]  for f < 5        (zero mode, L = 6: an axis of v coefficients gives 2 v - 4 samples)
+ *   pred[b, n, 5]  = IDWT1(lo, hi)[n] in every cell, lo[k], hi[k] = the means of xs[b, k, C - 1] over rows < half and rows >= half (all W
+ *                    columns), k < tc; the sums are fp64 of fp32 products, the means rounded to fp32
+ * pred [B][to][6][ho][wo] fp32, contiguous. A workgroup per (sample, field, tile of tn frames x hn rows, full width) runs the T, H and W
+ * passes with its intermediates in lds_bytes of LDS; cdiv(to, tn) more workgroups per sample write channel 5. Nothing is allocated; no
+ * atomics, every sum in a fixed order: a sample's bits do not depend on B or its index. x and pred must not overlap. tn, hn even;
+ * lds_bytes <= 64 KiB and what the layout needs (wdno_amd/smoke/reconstruct.py: plan). filt as for wdno_smoke_guidance.
+ * WDNO_EUNSUPPORTED for anything but mode 1 (zero) with L = 6 (bior1.3); WDNO_EINVAL for inconsistent integers: a block larger than the
+ * tensor, a crop larger than the reconstruction, tiles or an LDS size that do not fit. */
+typedef struct {
+  int B, F, C, H, W;                                            /* the tensor x */
+  int sample_stride, frame_stride, chan_stride, row_stride;     /* in elements; columns are contiguous */
+  int tc, hc, wc, to, ho, wo;                                   /* coefficient block (shape) and field size (ori_shape): to <= 2 tc - 4, ... */
+  int L, mode, half;
+  int tn, hn;
+  int lds_bytes;
+} wdno_smoke_reconstruct_desc;
+int wdno_smoke_reconstruct(const float* x, const float* rescaler, float* pred, const wdno_smoke_reconstruct_desc* d, const float* filt,
+                           wdno_stream_t s);
+
+/* wdno_smoke_score: the sums InferencePipeline.multi_evaluate (smoke/inference_2d.py:426-439) takes its metrics from, for one (pred, data)
+ * pair in one launch, one workgroup per sample. pred [B][T][6][h][w] fp32, contiguous. data: HOST pointer to six channel entries; channel
+ * c of the data at (b, t, row, col) is ptr[b sample_stride + t frame_stride + row row_stride + col col_stride], fp32 or fp64 (is_double);
+ * strides in elements, >= 0, a zero stride broadcasts. out [B][5] fp64, every difference formed as (double)pred - (double)data:
+ *   out[b][0] = sum (pred - data)^2 over channels 0..2      out[b][1] = sum (pred - data)^2 over channel 5
+ *   out[b][2] = sum data^2 over channels 0..2               out[b][3] = sum data^2 over channels 3..4
+ *   out[b][4] = data[b, T - 1, 5, 0, 0]
+ * Sums 0 and 2 leave out frame 0 of channel 0 (the reference's mask[:, 0, 0] = False). No atomics, a fixed order: a sample's result does
+ * not depend on B or its index. Nothing is allocated. WDNO_EINVAL for inconsistent integers, negative strides or misaligned pointers. */
+typedef struct {
+  const void* ptr;
+  long long sample_stride, frame_stride, row_stride, col_stride;
+  int is_double, reserved;
+} wdno_smoke_score_channel;
+int wdno_smoke_score(const float* pred, const wdno_smoke_score_channel* data, double* out, int B, int T, int h, int w, wdno_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,16 @@ class SmokeGenerateDesc(C.Structure):       # include/wdno_hip.h: wdno_smoke_gen
     _fields_ = [(k, I) for k in ('B', 'scenelength', 'record_scale', 'stride', 'max_iter', 'threads', 'noise_mode')] + [('accuracy', F), ('seed', C.c_uint64)]
 
 
+class SmokeReconstructDesc(C.Structure):    # include/wdno_hip.h: wdno_smoke_reconstruct_desc
+    _fields_ = [(k, I) for k in ('B', 'F', 'C', 'H', 'W', 'sample_stride', 'frame_stride', 'chan_stride', 'row_stride', 'tc', 'hc', 'wc', 'to', 'ho',
+                                 'wo', 'L', 'mode', 'half', 'tn', 'hn', 'lds_bytes')]
+
+
+class SmokeScoreChannel(C.Structure):       # include/wdno_hip.h: wdno_smoke_score_channel
+    _fields_ = [('ptr', C.c_void_p)] + [(k, C.c_longlong) for k in ('sample_stride', 'frame_stride', 'row_stride', 'col_stride')] + \
+               [('is_double', I), ('reserved', I)]
+
+
 PD, PG, PA, PC = C.POINTER(DwtDesc), C.POINTER(ConvGeom), C.POINTER(AttnDesc), C.POINTER(CondDesc)
 PF = C.POINTER(C.c_float)
 
@@ -214,6 +224,8 @@ PROTOTYPES = {
     'wdno_smoke_solve': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeSolveDesc), P]),
     'wdno_smoke_generate': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(SmokeGenerateDesc), P]),
     'wdno_smoke_noise': (I, [P, P, P, P, I, C.c_uint64, P, P]),
+    'wdno_smoke_reconstruct': (I, [P, P, P, C.POINTER(SmokeReconstructDesc), PF, P]),
+    'wdno_smoke_score': (I, [P, C.POINTER(SmokeScoreChannel), P, I, I, I, I, P]),
 }
 
 _lib = None
