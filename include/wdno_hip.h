@@ -204,6 +204,25 @@ int wdno_conv_fwd_f16x3_ws(const void* xh, const void* xl, const float* sx, cons
                            const float* bias, const float* residual, float* y, float* amax_rec, const wdno_conv_geom* g,
                            void* ws, size_t ws_bytes, wdno_stream_t s);
 size_t wdno_conv_fwd_split_ws_bytes(const wdno_conv_geom* g);
+/* Plan queries: which kernel the entry points above (and the weight-gradient ones below) would launch for a geometry, under the current debug
+ * mode. They launch nothing; the launch paths call the same choosing code. CU-dependent choices use the current device's CU count (256 when
+ * there is no device). lowp: 0 = (hi, lo) fp16 planes, 1 = single bf16 planes. residual_is_y: the residual operand is y itself (accumulation in place: the
+ * only way a residual changes the choice -- the two-block ksplit form adds onto zeroed outputs and is not taken then). split_ws_bytes:
+ * the workspace the caller would lend (wdno_conv_fwd_f16x3_ws), 0 = none.
+ * lowp < 0 asks about the exact-fp32 entry point wdno_conv_fwd (family WDNO_CONV_FP32, its tile); the same is reported where the split entry
+ * points refuse the geometry (C % 8 != 0) and the caller has to run wdno_conv_fwd.
+ * uniform: chunked DMA kernels only -- 1 = whole 32-channel blocks (one channel-block index per step), 0 = per-lane channel blocks; the
+ * tap-resident kernels always work on whole blocks (1), the others report 0. grid = blocks of the first grid dimension (the register-staged
+ * kernels add ksplit as the second); ntiles = pixel tiles x channel tiles. */
+enum { WDNO_CONV_FP32 = 0, WDNO_CONV_REG_H3 = 1, WDNO_CONV_CHUNKED_H3D = 2, WDNO_CONV_TAP_H3T = 3, WDNO_CONV_STEM_H3T = 4 };
+typedef struct { int family, bm, bn, uniform, tsplit, ksplit, ntiles, grid; } wdno_conv_plan;
+int wdno_conv_fwd_plan(const wdno_conv_geom* g, int lowp, int residual_is_y, size_t split_ws_bytes, wdno_conv_plan* out);
+/* family: register-staged (conv_wgrad_h3_kernel), chunked DMA (h3d), window (h3w, 3-wide taps on whole 64-channel tiles) or stem (h3s, 7-wide).
+ * reduce_tiled: the split reduction into the parameter layout dw[Kn][Cn][..] is the tiled one (Kn / Cn <= 0: g->K / g->C). items = work items
+ * of the launch, grid = its blocks (first dimension; the register-staged kernels add `splits` as the second). */
+enum { WDNO_WGRAD_REG_H3 = 0, WDNO_WGRAD_CHUNKED_H3D = 1, WDNO_WGRAD_WINDOW_H3W = 2, WDNO_WGRAD_STEM_H3S = 3 };
+typedef struct { int family, bm, bn, splits, pix_per_split, splitpair, reduce_tiled, items, grid; } wdno_wgrad_plan;
+int wdno_conv_wgrad_plan(const wdno_conv_geom* g, int lowp, int Kn, int Cn, wdno_wgrad_plan* out);
 /* weight gradient on the same split planes (g->C = C8 of x, g->K = K8 of dy); dwp [kd][kh][K8][kw*C8] fp32 */
 size_t wdno_conv_wgrad_f16x3_ws_bytes(const wdno_conv_geom* g);
 /* pixel_table: [N*OD*OH*OW] 16-byte records from wdno_conv_pixel_table (depends on the geometry only; callers cache it) */

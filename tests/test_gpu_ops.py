@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import conv_ref
 from tests.helpers import load_npz, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -155,6 +156,12 @@ def conv_case(ops, xs, ws, stride, padding, seed, transposed=False, bias=True, r
         assert rel_l2((from_cl(rd.grad.cpu())[:, :k] if nd else rd.grad.cpu()[..., :k]), rr.grad) < tol, 'residual grad'
 
 
+def library_plans(ops, xs, ws, stride, padding, residual=False):
+    """(forward, data gradient, weight gradient) plan strings from the library's own choosing code (wdno_conv_fwd_plan / wdno_conv_wgrad_plan
+    through tests/conv_ref.py), None where a pass does not run on a split kernel: what really decides, unlike the keys of ops.PROFILE."""
+    return conv_ref.plans(ops, conv_ref._c('adhoc', xs, ws, stride=stride, padding=padding, residual=residual))
+
+
 CONV_CASES = [
     # (x shape NC..., weight shape, stride, padding)
     ('3x3x3_64', (1, 64, 4, 10, 12), (64, 64, 3, 3, 3), 1, 1),
@@ -212,6 +219,8 @@ def test_conv_f16x3_path(ops, name, xs, ws, stride, padding):
     finally:
         ops.PROFILE = None
     assert any('h3' in k for k in n_launch), f'fp16-split kernel was not used: {list(n_launch)}'
+    plans = library_plans(ops, xs, ws, stride, padding)
+    assert plans[0] is not None and plans[0].split(':')[0] in ('h3', 'h3d', 'h3t', 'h3t_stem') and plans[2] is not None, plans
 
 
 @pytest.mark.parametrize('mode', [DBG_FORCE_DMA], ids=['dma'])
@@ -286,6 +295,8 @@ def test_conv_f16x3_split_reduction(ops, name, xs, ws, stride, padding, tag, res
     finally:
         ops.PROFILE = None
     assert any(k.endswith(tag) for k in n_launch), f'split reduction was not used: {list(n_launch)}'
+    plans = library_plans(ops, xs, ws, stride, padding, residual)
+    assert plans[0].startswith('h3t:128x128' + tag), plans
     x = dev(to_cl(g(xs, 5)).float().contiguous())
     w = dev(g(ws, 6, 0.02).float())
     y0 = ops.conv_cl(x, w, None, padding=padding)
@@ -313,6 +324,8 @@ def test_conv_patch2_dgrad_on_split_kernels(ops, xs, ws):
     finally:
         ops.PROFILE = None
     assert sum(len(v) for k, v in n_launch.items() if 'h3' in k) >= 5, list(n_launch)      # forward + four taps
+    plans = library_plans(ops, xs, ws, stride, 0)
+    assert all(p is not None and p.startswith('h3') for p in plans), plans                 # forward, the four-tap data gradient, weight gradient
     x = dev(to_cl(g(xs, 5)), grad=True)
     w = dev(g(ws, 6, 0.05))
     go = dev(to_cl(g((xs[0], ws[0], *[v // 2 if i >= len(xs) - 4 else v for i, v in enumerate(xs[2:])]), 7)))

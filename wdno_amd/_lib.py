@@ -43,6 +43,18 @@ class WgradReduceItem(C.Structure):          # include/wdno_hip.h: wdno_wgrad_re
                 ('tiled', I), ('reserved', I)]
 
 
+class ConvPlan(C.Structure):                 # include/wdno_hip.h: wdno_conv_plan
+    _fields_ = [(k, I) for k in ('family', 'bm', 'bn', 'uniform', 'tsplit', 'ksplit', 'ntiles', 'grid')]
+
+
+class ConvWgradPlan(C.Structure):            # include/wdno_hip.h: wdno_wgrad_plan
+    _fields_ = [(k, I) for k in ('family', 'bm', 'bn', 'splits', 'pix_per_split', 'splitpair', 'reduce_tiled', 'items', 'grid')]
+
+
+CONV_FAMILIES = ('fp32', 'h3', 'h3d', 'h3t', 'h3t_stem')          # WDNO_CONV_*
+WGRAD_FAMILIES = ('h3', 'h3d', 'h3w', 'h3s')                       # WDNO_WGRAD_*
+
+
 class RowsSumItem(C.Structure):              # include/wdno_hip.h: wdno_rows_sum_item
     _fields_ = [('part', C.c_void_p), ('out', C.c_void_p), ('rows', I), ('stride', I), ('col0', I), ('ncols', I), ('is_double', I), ('reserved', I)]
 
@@ -126,6 +138,8 @@ PROTOTYPES = {
     'wdno_conv_fwd_f16x3_ws': (I, [P, P, P, P, P, P, P, P, P, P, PG, P, Z, P]),
     'wdno_conv_fwd_split_ws_bytes': (Z, [PG]),
     'wdno_conv_wgrad_f16x3_ws_bytes': (Z, [PG]),
+    'wdno_conv_fwd_plan': (I, [PG, I, I, Z, P]),
+    'wdno_conv_wgrad_plan': (I, [PG, I, I, I, P]),
     'wdno_conv_pixel_table': (I, [P, PG, P]),
     'wdno_conv_wgrad_f16x3': (I, [P, P, P, P, P, P, P, P, P, Z, PG, P]),
     'wdno_conv_wgrad_f16x3_param': (I, [P, P, P, P, P, P, P, P, I, I, P, Z, PG, P]),

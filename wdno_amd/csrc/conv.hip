@@ -217,21 +217,50 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(const float* __restrict__
 }
 
 template <int BM, int BN, int WM, int WN, bool TWO_LEVEL = false>
-static int launch_fwd(const float* x, const float* wp, const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
+static int launch_fwd(const float* x, const float* wp, const float* bias, const float* residual, float* y, ConvP& p, const wdno_conv_plan& pl, hipStream_t st) {
   const wdno_conv_geom& g = p.g;
-  int64_t tiles_m = cdiv64(p.P, BM);
   p.tiles_n = cdiv(g.K, BN);
-  int64_t nt = tiles_m * p.tiles_n;
-  if (nt > 0x7fffffff) return WDNO_EUNSUPPORTED;
-  p.ntiles = (int)nt;
+  p.ntiles = pl.ntiles;
   size_t lds = (size_t)2 * (BM + BN) * LDS_STRIDE * sizeof(float);
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute((const void*)conv_fwd_kernel<BM, BN, WM, WN, TWO_LEVEL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_done = true;
   }
-  conv_fwd_kernel<BM, BN, WM, WN, TWO_LEVEL><<<p.ntiles, 256, lds, st>>>(x, wp, bias, residual, y, p);
+  conv_fwd_kernel<BM, BN, WM, WN, TWO_LEVEL><<<pl.grid, 256, lds, st>>>(x, wp, bias, residual, y, p);
   return WDNO_OK;
+}
+
+// tile choice of the exact-fp32 forward (wdno_conv_fwd launches it, wdno_conv_fwd_plan reports it): the largest tile that still yields >= 2
+// workgroups per CU (512); small problems take smaller tiles. *two_level: the two-level summation of long reductions.
+static int conv_fwd_fp32_choose(const ConvP& p, wdno_conv_plan& pl, bool* two_level) {
+  const int64_t P = p.P;
+  const int K = p.g.K;
+  auto blocks = [&](int bm, int bn) { return cdiv64(P, bm) * cdiv(K, bn); };
+  int bm, bn;
+  *two_level = p.nsteps >= 64;       // reductions of >= 2048 terms (the 7x7x7 stem: 15 092): two-level summation, see conv_fwd_kernel
+  if (*two_level) {
+    if (K > 64 && blocks(64, 128) >= 256) { bm = 64; bn = 128; }
+    else { bm = 64; bn = 64; }
+  } else if (K > 64) {
+    if (blocks(128, 128) >= 512 || blocks(64, 128) < 2 * blocks(128, 128)) { bm = 128; bn = 128; }
+    else { bm = 64; bn = 128; }
+  } else {
+    if (blocks(128, 64) >= 512 || P <= 128) { bm = 128; bn = 64; }
+    else { bm = 64; bn = 64; }
+  }
+  const int64_t nt = blocks(bm, bn);
+  if (nt > 0x7fffffff) return WDNO_EUNSUPPORTED;
+  pl.family = WDNO_CONV_FP32;
+  pl.bm = bm; pl.bn = bn; pl.uniform = 0; pl.tsplit = 1; pl.ksplit = 1;
+  pl.ntiles = (int)nt; pl.grid = (int)nt;
+  return WDNO_OK;
+}
+int wdno_conv_fwd_fp32_plan(const wdno_conv_geom* g, wdno_conv_plan* out) {
+  ConvP p;
+  fill_params(p, g);
+  bool two_level;
+  return conv_fwd_fp32_choose(p, *out, &two_level);
 }
 
 extern "C" int wdno_conv_fwd(const float* x, const float* wp, const float* bias, const float* residual, float* y,
@@ -241,19 +270,19 @@ extern "C" int wdno_conv_fwd(const float* x, const float* wp, const float* bias,
   ConvP p;
   fill_params(p, g);
   hipStream_t st = as_stream(s);
-  // tile choice: the largest tile that still yields >= 2 workgroups per CU (512); small problems take smaller tiles
-  const int64_t P = p.P;
-  const int K = g->K;
-  auto blocks = [&](int bm, int bn) { return cdiv64(P, bm) * cdiv(K, bn); };
-  if (p.nsteps >= 64) {       // reductions of >= 2048 terms (the 7x7x7 stem: 15 092): two-level summation, see conv_fwd_kernel
-    if (K > 64 && blocks(64, 128) >= 256) rc = launch_fwd<64, 128, 1, 4, true>(x, wp, bias, residual, y, p, st);
-    else rc = launch_fwd<64, 64, 2, 2, true>(x, wp, bias, residual, y, p, st);
-  } else if (K > 64) {
-    if (blocks(128, 128) >= 512 || blocks(64, 128) < 2 * blocks(128, 128)) rc = launch_fwd<128, 128, 2, 2>(x, wp, bias, residual, y, p, st);
-    else rc = launch_fwd<64, 128, 1, 4>(x, wp, bias, residual, y, p, st);
+  wdno_conv_plan pl;
+  bool two_level;
+  rc = conv_fwd_fp32_choose(p, pl, &two_level);
+  if (rc) return rc;
+  if (two_level) {
+    if (pl.bn == 128) rc = launch_fwd<64, 128, 1, 4, true>(x, wp, bias, residual, y, p, pl, st);
+    else rc = launch_fwd<64, 64, 2, 2, true>(x, wp, bias, residual, y, p, pl, st);
+  } else if (pl.bn == 128) {
+    if (pl.bm == 128) rc = launch_fwd<128, 128, 2, 2>(x, wp, bias, residual, y, p, pl, st);
+    else rc = launch_fwd<64, 128, 1, 4>(x, wp, bias, residual, y, p, pl, st);
   } else {
-    if (blocks(128, 64) >= 512 || P <= 128) rc = launch_fwd<128, 64, 4, 1>(x, wp, bias, residual, y, p, st);
-    else rc = launch_fwd<64, 64, 2, 2>(x, wp, bias, residual, y, p, st);
+    if (pl.bm == 128) rc = launch_fwd<128, 64, 4, 1>(x, wp, bias, residual, y, p, pl, st);
+    else rc = launch_fwd<64, 64, 2, 2>(x, wp, bias, residual, y, p, pl, st);
   }
   if (rc) return rc;
   return wdno_check_launch();

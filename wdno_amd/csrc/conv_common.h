@@ -62,14 +62,36 @@ static inline int check_geom(const wdno_conv_geom* g) {
 void wdno_wgrad_h3d_plan(const wdno_conv_geom* g, int* bm, int* bn, int* splits, int* pix_per_split, int* splitpair = nullptr);
 int wdno_conv_wgrad_h3_dma(const void* xh, const void* xl, const void* dyh, const void* dyl, const float* sx, const float* sdy,
                            const void* table, float* wsf, const wdno_conv_geom* g, hipStream_t st);
-// conv_h3d.hip: LDS-DMA variant of the split-fp16 forward / data-gradient kernel (WDNO_EUNSUPPORTED -> use conv_h3.hip's)
+// ... and what that launch would be (family, tiles, split plan, items, grid; reduce_tiled is the caller's), WDNO_EUNSUPPORTED as the launch
+int wdno_wgrad_h3d_describe(const wdno_conv_geom* g, wdno_wgrad_plan* out);
+// What the forward / data-gradient launch path decided for a geometry (the public wdno_conv_plan plus what the launchers need). Filled by the
+// choosers below -- the ONLY place where a kernel family, tile shape, split or grid is chosen; the launchers read it and choose nothing.
+struct ConvFwdChoice {
+  wdno_conv_plan plan;
+  int kw;         // tap-resident kernels: 3 or 7 (the stem)
+  int sp;         // tap-resident 128 x 128 kernel in its split-run form
+};
+// persistent kernels: one block per CU in multiples of the 8 XCDs (the LDS ring allows no more), never more blocks than items
+static inline int conv_persistent_grid(int64_t items) {
+  int grid = wdno_num_cus() & ~7;
+  if (grid < 8) grid = 8;
+  if (items < grid) grid = (int)items;
+  return grid;
+}
+// conv.hip: the exact-fp32 forward kernel's tile for a geometry
+int wdno_conv_fwd_fp32_plan(const wdno_conv_geom* g, wdno_conv_plan* out);
+// conv_h3d.hip: LDS-DMA variant of the split-fp16 forward / data-gradient kernel. The chooser returns WDNO_EUNSUPPORTED for what these kernels
+// do not take (-> conv_h3.hip's register-staged ones); lp = single bf16 planes
+int wdno_conv_fwd_h3_dma_choose(const ConvP& p, bool lp, ConvFwdChoice& c);
 int wdno_conv_fwd_h3_dma(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                         const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st, int stages);
-// conv_h3t.hip: tap-resident variant for stride-1 convolutions on equal grids (called by conv_h3d.hip with the tile shape it chose)
+                         const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st);
+// conv_h3t.hip: tap-resident variant for stride-1 convolutions on equal grids (conv_h3d.hip passes the tile shape its cost model chose, and
+// the run count of a split reduction it wants)
 bool wdno_conv_h3t_takes(const wdno_conv_geom& g);
 int wdno_conv_h3t_split(const wdno_conv_geom& g, int64_t P, int cus);
-int wdno_conv_fwd_h3_tap(int shape, const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                         const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st);
+int wdno_conv_fwd_h3_tap_choose(int shape, int tsplit, const ConvP& p, bool lp, ConvFwdChoice& c);
+int wdno_conv_fwd_h3_tap(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
+                         const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st);
 #ifdef __HIPCC__
 // s_waitcnt lgkmcnt(0) + s_barrier. The wait is the BUILTIN so that the compiler's own s_waitcnt bookkeeping sees it: behind an
 // asm-only wait it still counts the scalar loads of the previous tile's epilogue as possibly outstanding at the head of the

@@ -503,13 +503,11 @@ __global__ __launch_bounds__(256) void conv_fwd_h3_kernel(const _Float16* __rest
 
 template <int BM, int BN, int WM, int WN, bool LP>
 static int launch_h3(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                     const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
+                     const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st) {
   const wdno_conv_geom& g = p.g;
-  int64_t tiles_m = cdiv64(p.P, BM);
   p.tiles_n = cdiv(g.K, BN);
-  int64_t nt = tiles_m * p.tiles_n;
-  if (nt > 0x7fffffff) return WDNO_EUNSUPPORTED;
-  p.ntiles = (int)nt;
+  p.ntiles = c.plan.ntiles;
+  p.ksplit = c.plan.ksplit;
   size_t lds = (size_t)2 * (LP ? 1 : 2) * (BM + BN) * HST * sizeof(_Float16);
   static bool attr_done = false;
   if (!attr_done) {
@@ -518,19 +516,62 @@ static int launch_h3(const void* xh, const void* xl, const void* wh, const void*
   }
   const int64_t x_elems = (int64_t)g.N * g.D * g.H * g.W * g.C;
   const int64_t w_elems = (int64_t)g.kd * g.kh * g.K * p.R;
-  if (x_elems * 2 >= OOB_OFFSET || w_elems * 2 >= OOB_OFFSET || p.P >= 0x7fffffff) return WDNO_EUNSUPPORTED;   // 32-bit buffer offsets
   float* rec = p.amax_rec;
   if (p.ksplit > 1) {                     // partial sums are added onto zeros; the amax record is filled by a sweep afterwards
     if (hipMemsetAsync(y, 0, (size_t)p.P * g.K * sizeof(float), st) != hipSuccess) return WDNO_ELAUNCH;
     p.amax_rec = nullptr;
   }
-  conv_fwd_h3_kernel<BM, BN, WM, WN, LP><<<dim3((unsigned)p.ntiles, (unsigned)p.ksplit), 256, lds, st>>>(
+  conv_fwd_h3_kernel<BM, BN, WM, WN, LP><<<dim3((unsigned)c.plan.grid, (unsigned)p.ksplit), 256, lds, st>>>(
       (const _Float16*)xh, (const _Float16*)xl, (const _Float16*)wh, (const _Float16*)wl, sx, sw, bias, residual, y, p,
       (unsigned)(x_elems * 2), (unsigned)(w_elems * 2));
   if (p.ksplit > 1 && rec) {
     amax_kernel<true><<<stream_grid(p.P * g.K / 16 + 1, 256), 256, 0, st>>>(y, p.P * g.K, reinterpret_cast<unsigned*>(rec));
     p.amax_rec = rec;
   }
+  return WDNO_OK;
+}
+
+// THE choice of the forward / data-gradient kernel: family, tile, splits and grid for the geometry in p (p.split_ws_bytes = what the caller
+// lends for a split reduction). conv_fwd_16 launches what this says and wdno_conv_fwd_plan reports it. res_is_y: the residual is y itself.
+static int conv_fwd_choose(const ConvP& p, bool lp, bool res_is_y, ConvFwdChoice& c) {
+  const wdno_conv_geom* g = &p.g;
+  const int64_t P = p.P;
+  const int K = g->K;
+  auto blocks = [&](int bm, int bn) { return cdiv64(P, bm) * cdiv(K, bn); };
+  // problems with at least 100 tiles: persistent LDS-DMA kernels (256x64 / 128x128 tiles, 64x64 per compute wave); even with
+  // fewer tiles than CUs they beat the register-staged kernels (l2 512->128: 0.36 -> 0.24 ms). WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV = never, _FORCE_DMA_CONV = always, _CHUNKED_DMA_CONV = always and not the tap-resident variant, _FORCE_TILES_160 / _320 = always with the five-row tile shapes (conv_h3d.hip)
+  const int dbg = wdno_debug_mode;
+  // ... and the tap-resident kernel (stride 1, equal grids, 3-wide) has 64 x 64 / 128 x 64 tiles for problems of fewer tiles
+  const bool small_tap = p.identity_out && wdno_conv_h3t_takes(*g) && g->kw == 3 && blocks(64, 64) >= 64;
+  if (dbg != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV && (dbg == WDNO_DBG_FORCE_DMA_CONV || dbg == WDNO_DBG_CHUNKED_DMA_CONV || dbg == WDNO_DBG_FORCE_TILES_160 || dbg == WDNO_DBG_FORCE_TILES_320 || small_tap || (K > 64 ? blocks(128, 128) : blocks(256, 64)) >= 100)) {
+    int rc = wdno_conv_fwd_h3_dma_choose(p, lp, c);
+    if (rc != WDNO_EUNSUPPORTED) return rc;
+  }
+  int bm, bn, ksplit = 1;
+  if (K > 64) {
+    if (blocks(128, 128) >= 512 || blocks(64, 128) < 2 * blocks(128, 128)) { bm = 128; bn = 128; }
+    // fewer 64 x 128 tiles than CUs (the 8 x 8 level of the Burgers U-Net at batch 16: 128 tiles of 288 steps each): 64 x 64 tiles
+    else if (blocks(64, 128) < 200) {
+      // ... and when even those leave CUs with a single block of several hundred steps, two blocks per tile (split over the tap rows)
+      if (blocks(64, 64) <= 384 && g->kd * g->kh >= 2 && p.nsteps >= 64 && p.identity_out && !res_is_y && !lp) ksplit = 2;
+      bm = 64; bn = 64;
+    }
+    else { bm = 64; bn = 128; }
+  } else {
+    if (blocks(128, 64) >= 512 || P <= 128) { bm = 128; bn = 64; }
+    else { bm = 64; bn = 64; }
+  }
+  const int64_t nt = blocks(bm, bn);
+  const int64_t x_elems = (int64_t)g->N * g->D * g->H * g->W * g->C;
+  const int64_t w_elems = (int64_t)g->kd * g->kh * g->K * p.R;
+  if (nt > 0x7fffffff || x_elems * 2 >= OOB_OFFSET || w_elems * 2 >= OOB_OFFSET || p.P >= 0x7fffffff) return WDNO_EUNSUPPORTED;   // 32-bit buffer offsets
+  c.kw = g->kw; c.sp = 0;
+  c.plan.family = WDNO_CONV_REG_H3;
+  c.plan.bm = bm; c.plan.bn = bn;
+  c.plan.uniform = 0;
+  c.plan.tsplit = 1; c.plan.ksplit = ksplit;
+  c.plan.ntiles = (int)nt;
+  c.plan.grid = (int)nt;
   return WDNO_OK;
 }
 
@@ -559,32 +600,19 @@ static int conv_fwd_16(const void* xh, const void* xl, const float* sx, const vo
   p.nchunk = cdiv(p.R, HBK);
   p.nsteps = g->kd * g->kh * p.nchunk;
   hipStream_t st = as_stream(s);
-  const int64_t P = p.P;
-  const int K = g->K;
-  auto blocks = [&](int bm, int bn) { return cdiv64(P, bm) * cdiv(K, bn); };
-  // problems with at least 100 tiles: persistent LDS-DMA kernels (256x64 / 128x128 tiles, 64x64 per compute wave); even with
-  // fewer tiles than CUs they beat the register-staged kernels (l2 512->128: 0.36 -> 0.24 ms). WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV = never, _FORCE_DMA_CONV = always, _CHUNKED_DMA_CONV = always and not the tap-resident variant, _FORCE_TILES_160 / _320 = always with the five-row tile shapes (conv_h3d.hip)
-  const int dbg = wdno_debug_mode;
-  // ... and the tap-resident kernel (stride 1, equal grids, 3-wide) has 64 x 64 / 128 x 64 tiles for problems of fewer tiles
-  const bool small_tap = p.identity_out && wdno_conv_h3t_takes(*g) && g->kw == 3 && blocks(64, 64) >= 64;
-  if (dbg != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV && (dbg == WDNO_DBG_FORCE_DMA_CONV || dbg == WDNO_DBG_CHUNKED_DMA_CONV || dbg == WDNO_DBG_FORCE_TILES_160 || dbg == WDNO_DBG_FORCE_TILES_320 || small_tap || (K > 64 ? blocks(128, 128) : blocks(256, 64)) >= 100)) {
-    rc = wdno_conv_fwd_h3_dma(xh, LP ? nullptr : xl, wph, LP ? nullptr : wpl, sx, sw, bias, residual, y, p, st, 3);
-    if (rc == WDNO_OK) return wdno_check_launch();
-    if (rc != WDNO_EUNSUPPORTED) return rc;
+  ConvFwdChoice c;
+  rc = conv_fwd_choose(p, LP, residual != nullptr && residual == y, c);
+  if (rc) return rc;
+  if (c.plan.family != WDNO_CONV_REG_H3) {
+    rc = wdno_conv_fwd_h3_dma(xh, LP ? nullptr : xl, wph, LP ? nullptr : wpl, sx, sw, bias, residual, y, p, c, st);
+    if (rc) return rc;
+    return wdno_check_launch();
   }
-  if (K > 64) {
-    if (blocks(128, 128) >= 512 || blocks(64, 128) < 2 * blocks(128, 128)) rc = launch_h3<128, 128, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
-    // fewer 64 x 128 tiles than CUs (the 8 x 8 level of the Burgers U-Net at batch 16: 128 tiles of 288 steps each): 64 x 64 tiles
-    else if (blocks(64, 128) < 200) {
-      // ... and when even those leave CUs with a single block of several hundred steps, two blocks per tile (split over the tap rows)
-      if (blocks(64, 64) <= 384 && g->kd * g->kh >= 2 && p.nsteps >= 64 && p.identity_out && residual != y && !LP) p.ksplit = 2;
-      rc = launch_h3<64, 64, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
-    }
-    else rc = launch_h3<64, 128, 1, 4, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
-  } else {
-    if (blocks(128, 64) >= 512 || P <= 128) rc = launch_h3<128, 64, 4, 1, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
-    else rc = launch_h3<64, 64, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, st);
-  }
+  const int bm = c.plan.bm, bn = c.plan.bn;
+  if (bm == 128 && bn == 128) rc = launch_h3<128, 128, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, c, st);
+  else if (bm == 64 && bn == 128) rc = launch_h3<64, 128, 1, 4, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, c, st);
+  else if (bm == 128 && bn == 64) rc = launch_h3<128, 64, 4, 1, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, c, st);
+  else rc = launch_h3<64, 64, 2, 2, LP>(xh, xl, wph, wpl, sx, sw, bias, residual, y, p, c, st);
   if (rc) return rc;
   return wdno_check_launch();
 }
@@ -620,6 +648,22 @@ extern "C" size_t wdno_conv_fwd_split_ws_bytes(const wdno_conv_geom* g) {
   if (!p.identity_out || !wdno_conv_h3t_takes(*g)) return 0;
   const int runs = wdno_conv_h3t_split(*g, p.P, wdno_num_cus() & ~7);
   return runs > 1 ? (size_t)runs * p.P * g->K * sizeof(float) : 0;
+}
+extern "C" int wdno_conv_fwd_plan(const wdno_conv_geom* g, int lowp, int residual_is_y, size_t split_ws_bytes, wdno_conv_plan* out) {
+  WDNO_REQUIRE(out);
+  int rc = check_geom(g);
+  if (rc) return rc;
+  if (lowp < 0 || (g->C & 7)) return wdno_conv_fwd_fp32_plan(g, out);
+  ConvP p;
+  fill_params(p, g);
+  p.split_ws_bytes = split_ws_bytes;
+  p.nchunk = cdiv(p.R, HBK);
+  p.nsteps = g->kd * g->kh * p.nchunk;
+  ConvFwdChoice c;
+  rc = conv_fwd_choose(p, lowp != 0, residual_is_y != 0, c);
+  if (rc) return rc;
+  *out = c.plan;
+  return WDNO_OK;
 }
 extern "C" int wdno_conv_fwd_bf16(const void* x16, const void* wp16, const float* bias, const float* residual, float* y, float* amax_rec,
                                   const wdno_conv_geom* g, wdno_stream_t s) {
@@ -949,6 +993,25 @@ static void launch_wgrad_h3(const void* xh, const void* xl, const void* dyh, con
   conv_wgrad_h3_kernel<BM, BN, WM, WN, LP><<<grid, 256, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)dyh,
                                                             (const _Float16*)dyl, sx, sdy, (const int4v*)table, wsf, w, x_bytes, dy_bytes);
 }
+// THE choice of the weight-gradient kernel: the persistent LDS-DMA kernels for everything they take (WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV = never),
+// the register-staged kernels below otherwise. wgrad_h3_partials launches what this says and wdno_conv_wgrad_plan() reports it (reduce_tiled is
+// filled there: it depends on the parameter's extents).
+static int wgrad_h3_choose(const wdno_conv_geom* g, WgradHP& w, wdno_wgrad_plan& pl) {
+  wgrad_h3_plan(w, g);
+  pl.reduce_tiled = 0;
+  if (wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {
+    int rc = wdno_wgrad_h3d_describe(g, &pl);
+    if (rc != WDNO_EUNSUPPORTED) return rc;
+  }
+  if (w.splits > 65535) return WDNO_EUNSUPPORTED;
+  pl.family = WDNO_WGRAD_REG_H3;
+  pl.bm = g->K > 64 ? 128 : 64;
+  pl.bn = w.bn;
+  pl.splits = w.splits; pl.pix_per_split = (int)w.pix_per_split; pl.splitpair = 0;
+  pl.items = w.tiles_k * g->kd * g->kh * w.tiles_r;
+  pl.grid = pl.items;
+  return WDNO_OK;
+}
 // Runs the weight-gradient kernels; the per-split partial results go to `ws` ([splits][ntap][K][R]; with one split `single`
 // may name the final packed destination instead). Returns the split count through *splits_out.
 static int wgrad_h3_partials(const void* xh, const void* xl, const float* sx, const void* dyh, const void* dyl, const float* sdy,
@@ -960,17 +1023,17 @@ static int wgrad_h3_partials(const void* xh, const void* xl, const float* sx, co
   if ((int64_t)g->N * g->D * g->H * g->W * g->C * 2 >= OOB_OFFSET || (int64_t)g->N * g->YD * g->YH * g->YW * g->K * 2 >= OOB_OFFSET)
     return WDNO_EUNSUPPORTED;        // 32-bit buffer offsets
   WgradHP w;
-  wgrad_h3_plan(w, g);
-  // persistent LDS-DMA kernel for everything it takes (WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV = never); the register-staged kernels below are the fallback
-  if (wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {
-    int bm, bn, splits, pps, sp_mode;
-    wdno_wgrad_h3d_plan(g, &bm, &bn, &splits, &pps, &sp_mode);
+  wdno_wgrad_plan pl;
+  rc = wgrad_h3_choose(g, w, pl);
+  if (rc) return rc;
+  if (pl.family != WDNO_WGRAD_REG_H3) {
+    const int splits = pl.splits;
     size_t need_d = (size_t)splits * g->kd * g->kh * (size_t)g->K * w.c.R * sizeof(float);
     float* dst = (splits == 1 && single) ? single : (float*)ws;
     if (dst == (float*)ws && ws_bytes < need_d) return WDNO_EWORKSPACE;
     rc = wdno_conv_wgrad_h3_dma(xh, xl, dyh, dyl, sx, sdy, pixel_table, dst, g, st);
-    if (rc == WDNO_OK) { *splits_out = splits; return WDNO_OK; }
-    if (rc != WDNO_EUNSUPPORTED) return rc;
+    if (rc == WDNO_OK) *splits_out = splits;
+    return rc;
   }
   size_t need = (size_t)w.splits * g->kd * g->kh * (size_t)g->K * w.c.R * sizeof(float);
   float* wsf = (w.splits == 1 && single) ? single : (float*)ws;
@@ -978,10 +1041,10 @@ static int wgrad_h3_partials(const void* xh, const void* xl, const float* sx, co
   if (w.splits > 65535) return WDNO_EUNSUPPORTED;
   dim3 grid((unsigned)(w.tiles_k * g->kd * g->kh * w.tiles_r), (unsigned)w.splits);
   if (xl == nullptr) {          // single bf16 plane per operand
-    if (g->K > 64) launch_wgrad_h3<128, 192, 2, 2, true>(xh, xh, dyh, dyh, sx, sdy, pixel_table, wsf, w, grid, st);
+    if (pl.bm == 128) launch_wgrad_h3<128, 192, 2, 2, true>(xh, xh, dyh, dyh, sx, sdy, pixel_table, wsf, w, grid, st);
     else if (w.bn == 192) launch_wgrad_h3<64, 192, 2, 2, true>(xh, xh, dyh, dyh, sx, sdy, pixel_table, wsf, w, grid, st);
     else launch_wgrad_h3<64, 128, 1, 4, true>(xh, xh, dyh, dyh, sx, sdy, pixel_table, wsf, w, grid, st);
-  } else if (g->K > 64) launch_wgrad_h3<128, 192, 2, 2, false>(xh, xl, dyh, dyl, sx, sdy, pixel_table, wsf, w, grid, st);
+  } else if (pl.bm == 128) launch_wgrad_h3<128, 192, 2, 2, false>(xh, xl, dyh, dyl, sx, sdy, pixel_table, wsf, w, grid, st);
   else if (w.bn == 192) launch_wgrad_h3<64, 192, 2, 2, false>(xh, xl, dyh, dyl, sx, sdy, pixel_table, wsf, w, grid, st);
   else launch_wgrad_h3<64, 128, 1, 4, false>(xh, xl, dyh, dyl, sx, sdy, pixel_table, wsf, w, grid, st);
   *splits_out = w.splits;
@@ -1089,6 +1152,18 @@ static bool wgrad_h3_reduce_tiled(int splits, const wdno_conv_geom* g, int Kn, i
   const int T = g->kd * g->kh * g->kw;
   const bool big = (int64_t)Kn * cdiv(Cn, 64) >= 512 && splits <= 8;
   return T <= 64 && (splits <= 2 || big);
+}
+extern "C" int wdno_conv_wgrad_plan(const wdno_conv_geom* g, int lowp, int Kn, int Cn, wdno_wgrad_plan* out) {
+  (void)lowp;                // (both plane forms share one plan)
+  WDNO_REQUIRE(out);
+  int rc = check_geom(g);
+  if (rc) return rc;
+  if ((g->C & 7) || (g->K & 7)) return WDNO_EUNSUPPORTED;
+  WgradHP w;
+  rc = wgrad_h3_choose(g, w, *out);
+  if (rc) return rc;
+  out->reduce_tiled = wgrad_h3_reduce_tiled(out->splits, g, Kn > 0 ? Kn : g->K, Cn > 0 ? Cn : g->C) ? 1 : 0;
+  return WDNO_OK;
 }
 
 // ---- every pending split reduction of a backward pass in ONE launch (round 6). A training step ran 58 of these reductions, 5-10 us each, one behind

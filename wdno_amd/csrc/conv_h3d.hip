@@ -338,22 +338,15 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
 
 template <int BM, int BN, int WM, int WN, int NS, bool LP>
 static int launch_h3d(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                      const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
+                      const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st) {
   const wdno_conv_geom& g = p.g;
-  int64_t tiles_m = cdiv64(p.P, BM);
   p.tiles_n = cdiv(g.K, BN);
-  int64_t nt = tiles_m * p.tiles_n;
-  if (nt > 0x7fffffff) return WDNO_EUNSUPPORTED;
-  p.ntiles = (int)nt;
+  p.ntiles = c.plan.ntiles;
   const size_t lds = (size_t)NS * (LP ? 1 : 2) * (BM + BN) * 64;
   const int64_t x_elems = (int64_t)g.N * g.D * g.H * g.W * g.C;
   const int64_t w_elems = (int64_t)g.kd * g.kh * g.K * p.R;
-  if (x_elems * 2 >= DMA_OOB || w_elems * 2 >= DMA_OOB || p.P >= 0x7fffffff) return WDNO_EUNSUPPORTED;
-  int grid = wdno_num_cus() & ~7;                      // one persistent block per CU (the LDS ring allows no more), multiple of the 8 XCDs
-  if (grid < 8) grid = 8;
-  if (p.ntiles < grid) grid = p.ntiles;
-  const bool uni = (g.C % 32) == 0;
-  if (uni) {
+  const int grid = c.plan.grid;
+  if (c.plan.uniform) {
     static bool done = false;
     if (!done) { (void)hipFuncSetAttribute((const void*)conv_fwd_h3d_kernel<BM, BN, WM, WN, NS, true, LP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
     conv_fwd_h3d_kernel<BM, BN, WM, WN, NS, true, LP><<<grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)wh, (const _Float16*)wl,
@@ -367,11 +360,9 @@ static int launch_h3d(const void* xh, const void* xl, const void* wh, const void
   return WDNO_OK;
 }
 
-// Returns WDNO_EUNSUPPORTED when the geometry is outside what the DMA kernels handle (the caller then uses the
+// The choice among the DMA kernels. Returns WDNO_EUNSUPPORTED when the geometry is outside what they handle (the caller then uses the
 // register-staged kernels of conv_h3.hip).
-template <bool LP>
-static int fwd_h3_dma(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                      const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
+int wdno_conv_fwd_h3_dma_choose(const ConvP& p, bool lp, ConvFwdChoice& c) {
   const wdno_conv_geom& g = p.g;
   if (g.kd > 8 || g.kh > 8 || g.kw > 8 || g.C < 8) return WDNO_EUNSUPPORTED;
   // Tile shape: the one with the least (rounds of the persistent grid) x (tile area), lightly weighted by how much operand
@@ -384,22 +375,23 @@ static int fwd_h3_dma(const void* xh, const void* xl, const void* wh, const void
   };
   const bool narrow_only = g.K <= 64;
   int best = narrow_only ? 2 : 0;
-  double c = narrow_only ? cost(256, 64, 1.04) : cost(128, 128, 1.0);
-  if (!narrow_only && cost(192, 128, 1.0) < c) { best = 1; c = cost(192, 128, 1.0); }
-  if (!narrow_only && cost(256, 64, 1.04) < c) { best = 2; c = cost(256, 64, 1.04); }
-  if (cost(192, 64, 1.08) < c) { best = 3; c = cost(192, 64, 1.08); }
+  double cbest = narrow_only ? cost(256, 64, 1.04) : cost(128, 128, 1.0);
+  if (!narrow_only && cost(192, 128, 1.0) < cbest) { best = 1; cbest = cost(192, 128, 1.0); }
+  if (!narrow_only && cost(256, 64, 1.04) < cbest) { best = 2; cbest = cost(256, 64, 1.04); }
+  if (cost(192, 64, 1.08) < cbest) { best = 3; cbest = cost(192, 64, 1.08); }
   if (p.identity_out && wdno_conv_h3t_takes(g)) {
     // tap-resident kernel only: two more shapes of 20480 outputs, five MFMA row tiles per wave. On 256 CUs the 20 x 20-level layers with 128
     // output channels are 600 tiles of 128 x 128 (three rounds, the last with 88 tiles) but 480 of 160 x 128 (two rounds, 94 % full), the
     // 10 x 10-level ones with 256 are 200 of 192 x 128 (78 % of one round) but 240 of 160 x 128; 320 x 64 does the same for 64 output
     // channels at the 20 x 20 level (240 tiles instead of 400 of 192 x 64).
+    int tsplit = 1;
     if (g.kw == 3) {
-      if (!narrow_only && cost(160, 128, 1.02) < c) { best = 4; c = cost(160, 128, 1.02); }
-      if (cost(320, 64, 1.05) < c) { best = 5; c = cost(320, 64, 1.05); }
+      if (!narrow_only && cost(160, 128, 1.02) < cbest) { best = 4; cbest = cost(160, 128, 1.02); }
+      if (cost(320, 64, 1.05) < cbest) { best = 5; cbest = cost(320, 64, 1.05); }
       // few pixels x many channels (the 16 x 16 and 8 x 8 levels of the Burgers U-Net at batch 16: 176 tiles of 192 x 64, 64 of 128 x 128):
       // 128 x 64 and 64 x 64 tiles fill the chip; their operand traffic per MFMA is higher (weights 1.15 / 1.35).
-      if (cost(128, 64, 1.15) < c) { best = 7; c = cost(128, 64, 1.15); }
-      if (cost(64, 64, 1.35) < c) { best = 6; c = cost(64, 64, 1.35); }
+      if (cost(128, 64, 1.15) < cbest) { best = 7; cbest = cost(128, 64, 1.15); }
+      if (cost(64, 64, 1.35) < cbest) { best = 6; cbest = cost(64, 64, 1.35); }
       if (wdno_debug_mode == WDNO_DBG_FORCE_TILES_160) best = narrow_only ? 5 : 4;     // tests: the new shapes on small cases
       if (wdno_debug_mode == WDNO_DBG_FORCE_TILES_320) best = 5;
       // ... but where those small tiles were chosen for a LONG reduction (8 x 8 x 16 samples x 1024 channels: 256 tiles of 64 x 64 with 96 stages
@@ -408,20 +400,40 @@ static int fwd_h3_dma(const void* xh, const void* xl, const void* wh, const void
       // (Not where 128 x 64 tiles were chosen -- 16 x 16 x 16 samples x 512 channels: 61 us unsplit, 63 us as two runs.) Needs the caller's
       // workspace for the partial sums (wdno_conv_fwd_split_ws_bytes).
       const int split = wdno_conv_h3t_split(g, p.P, cus);
-      if (best == 6 && split > 1 && p.split_ws && (size_t)split * p.P * g.K * sizeof(float) <= p.split_ws_bytes) { best = 0; p.tsplit = split; }
+      if (best == 6 && split > 1 && p.split_ws_bytes && (size_t)split * p.P * g.K * sizeof(float) <= p.split_ws_bytes) { best = 0; tsplit = split; }
     }
-    return wdno_conv_fwd_h3_tap(best, xh, LP ? nullptr : xl, wh, wl, sx, sw, bias, residual, y, p, st);
+    return wdno_conv_fwd_h3_tap_choose(best, tsplit, p, lp, c);
   }
+  static const int shapes[4][2] = {{128, 128}, {192, 128}, {256, 64}, {192, 64}};
+  const int bm = shapes[best][0], bn = shapes[best][1];
+  const int64_t nt = cdiv64(p.P, bm) * cdiv(g.K, bn);
+  const int64_t x_elems = (int64_t)g.N * g.D * g.H * g.W * g.C;
+  const int64_t w_elems = (int64_t)g.kd * g.kh * g.K * p.R;
+  if (nt > 0x7fffffff || x_elems * 2 >= DMA_OOB || w_elems * 2 >= DMA_OOB || p.P >= 0x7fffffff) return WDNO_EUNSUPPORTED;
+  c.kw = g.kw; c.sp = 0;
+  c.plan.family = WDNO_CONV_CHUNKED_H3D;
+  c.plan.bm = bm; c.plan.bn = bn;
+  c.plan.uniform = (g.C % 32) == 0;
+  c.plan.tsplit = 1; c.plan.ksplit = 1;
+  c.plan.ntiles = (int)nt;
+  c.plan.grid = conv_persistent_grid(nt);
+  return WDNO_OK;
+}
+template <bool LP>
+static int fwd_h3_dma(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
+                      const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st) {
   // (deeper rings -- NS = 4 / 5 fill the 160 KB -- measured no faster: the 7 x 7 x 7 init convolution keeps its 3.1 M shader cycles)
-  if (best == 0) return launch_h3d<128, 128, 2, 2, 3, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  if (best == 1) return launch_h3d<192, 128, 2, 2, 3, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  if (best == 3) return launch_h3d<192, 64, 2, 2, 3, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  return launch_h3d<256, 64, 4, 1, 3, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
+  const int bm = c.plan.bm, bn = c.plan.bn;
+  if (bm == 128 && bn == 128) return launch_h3d<128, 128, 2, 2, 3, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 192 && bn == 128) return launch_h3d<192, 128, 2, 2, 3, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 192 && bn == 64) return launch_h3d<192, 64, 2, 2, 3, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 256 && bn == 64) return launch_h3d<256, 64, 4, 1, 3, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  return WDNO_EINVAL;
 }
 // xl / wl / sx / sw == nullptr selects the single-plane bf16 kernels (LP)
 int wdno_conv_fwd_h3_dma(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                         const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st, int stages) {
-  (void)stages;
-  if (xl == nullptr) return fwd_h3_dma<true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
-  return fwd_h3_dma<false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
+                         const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st) {
+  if (c.plan.family != WDNO_CONV_CHUNKED_H3D) return wdno_conv_fwd_h3_tap(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (xl == nullptr) return fwd_h3_dma<true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, c, st);
+  return fwd_h3_dma<false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
 }

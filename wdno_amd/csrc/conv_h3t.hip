@@ -554,30 +554,24 @@ __global__ __launch_bounds__(256) void conv_split_reduce_kernel(const float4* __
 
 template <int BM, int BN, int WM, int WN, int KW, int CB, bool LP, bool SP = false>
 static int launch_h3t(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                      const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
+                      const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st) {
   using S = TapShape<BM, BN, KW, CB>;
   const wdno_conv_geom& g = p.g;
-  int64_t tiles_m = cdiv64(p.P, BM);
   p.tiles_n = cdiv(g.K, BN);
-  int64_t nt = tiles_m * p.tiles_n;
-  if (nt > 0x7fffffff) return WDNO_EUNSUPPORTED;
-  p.ntiles = (int)nt;
+  p.ntiles = c.plan.ntiles;
+  p.tsplit = c.plan.tsplit;
   constexpr size_t lds = (size_t)2 * (LP ? 1 : 2) * (S::A_PLANE + S::B_PLANE);
   static_assert(lds <= 160 * 1024, "two stages must fit the LDS");
   const int64_t x_elems = (int64_t)g.N * g.D * g.H * g.W * g.C;
   const int64_t w_elems = (int64_t)g.kd * g.kh * g.K * p.R;
-  if (x_elems * 2 >= T_OOB || w_elems * 2 >= T_OOB || p.P >= 0x7fffffff - BM) return WDNO_EUNSUPPORTED;
   if (SP) {                                       // (conv_h3d.hip asks for it on whole 32-channel blocks and 3-wide taps only)
     const int nst = g.kd * g.kh * ((g.C + CB - 1) / CB);
     if (p.tsplit < 2 || ((CB / 16) * KW & 1) || nst % p.tsplit || !p.split_ws || (size_t)p.tsplit * p.P * g.K * sizeof(float) > p.split_ws_bytes || (g.K & 3))
       return WDNO_EINVAL;
-  } else p.tsplit = 1;
-  int grid = wdno_num_cus() & ~7;
-  if (grid < 8) grid = 8;
-  if ((int64_t)p.ntiles * p.tsplit < grid) grid = p.ntiles * p.tsplit;
+  }
   static bool done = false;
   if (!done) { (void)hipFuncSetAttribute((const void*)conv_fwd_h3t_kernel<BM, BN, WM, WN, KW, CB, LP, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
-  conv_fwd_h3t_kernel<BM, BN, WM, WN, KW, CB, LP, SP><<<grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)wh, (const _Float16*)wl,
+  conv_fwd_h3t_kernel<BM, BN, WM, WN, KW, CB, LP, SP><<<c.plan.grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)wh, (const _Float16*)wl,
                                                                     sx, sw, bias, residual, y, p, (unsigned)(x_elems * 2), (unsigned)(w_elems * 2));
   if (p.tsplit > 1) {
     const int64_t n4 = p.P * g.K / 4;
@@ -607,36 +601,64 @@ int wdno_conv_h3t_split(const wdno_conv_geom& g, int64_t P, int cus) {
   const int nst = g.kd * g.kh * (g.C / 32);
   return t128 * 4 <= cus && nst % 4 == 0 && nst / 4 >= 8 ? 4 : 1;
 }
-template <bool LP>
-static int fwd_h3t(int shape, const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                   const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
-  if (shape == 0 && p.tsplit > 1 && !LP) return launch_h3t<128, 128, 2, 2, 3, 32, false, true>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  if (shape == 0) return launch_h3t<128, 128, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  if (shape == 1) return launch_h3t<192, 128, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  if (shape == 3) return launch_h3t<192, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  if (shape == 4) return launch_h3t<160, 128, 1, 4, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  if (shape == 5) return launch_h3t<320, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  if (shape == 6) return launch_h3t<64, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);      // few pixels x many channels (Burgers 8 x 8 level)
-  if (shape == 7) return launch_h3t<128, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-  return launch_h3t<256, 64, 4, 1, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-}
-int wdno_conv_fwd_h3_tap(int shape, const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
-                         const float* bias, const float* residual, float* y, ConvP& p, hipStream_t st) {
-  // single-plane (bf16) mode has a third of the MFMA work per operand byte: with >= 128 output channels and enough tiles, 256 x 128
-  // tiles (64 x 128 per wave: 6 fragment reads per 8 MFMAs, 41 KB per stage)
-  if (p.g.kw == 7) {
-    const int ncb = (p.g.C + 15) / 16;
-    if (p.zb_blocks >= ncb) p.zb_blocks = ncb - 1;          // (a tile must keep at least its centre stage: t_live_stages)
+// The tile of a tap-resident launch. shape = what conv_h3d.hip's cost model chose (0 = 128 x 128, 1 = 192 x 128, 2 = 256 x 64, 3 = 192 x 64,
+// 4 = 160 x 128, 5 = 320 x 64, 6 = 64 x 64, 7 = 128 x 64), tsplit = the run count it wants for shape 0; both give way to the stem's own tiles
+// and to the wide tiles of the single-plane mode.
+int wdno_conv_fwd_h3_tap_choose(int shape, int tsplit, const ConvP& p, bool lp, ConvFwdChoice& c) {
+  const wdno_conv_geom& g = p.g;
+  static const int shapes[8][2] = {{128, 128}, {192, 128}, {256, 64}, {192, 64}, {160, 128}, {320, 64}, {64, 64}, {128, 64}};
+  int bm = shapes[shape & 7][0], bn = shapes[shape & 7][1];
+  c.kw = g.kw == 7 ? 7 : 3;
+  c.sp = 0;
+  c.plan.family = g.kw == 7 ? WDNO_CONV_STEM_H3T : WDNO_CONV_TAP_H3T;
+  if (g.kw == 7) {
     // less than one round of 256-pixel tiles (the stem at batch 1: 150 tiles on 256 CUs): 192-pixel tiles fill the chip and end a quarter
     // earlier (128-pixel tiles would need a second round) -- WDNO_DBG_STEM_TILES_256: the 256-pixel tiles always
     const int cus = wdno_num_cus();
-    if (xl != nullptr && cdiv64(p.P, 256) < cus && cdiv64(p.P, 192) <= cus && cdiv64(p.P, 192) > cdiv64(p.P, 256) && wdno_debug_mode != WDNO_DBG_STEM_TILES_256)
-      return launch_h3t<192, 64, 2, 2, 7, 16, false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
-    if (xl == nullptr) return launch_h3t<256, 64, 4, 1, 7, 16, true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
-    return launch_h3t<256, 64, 4, 1, 7, 16, false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
+    bn = 64;
+    bm = (!lp && cdiv64(p.P, 256) < cus && cdiv64(p.P, 192) <= cus && cdiv64(p.P, 192) > cdiv64(p.P, 256) && wdno_debug_mode != WDNO_DBG_STEM_TILES_256) ? 192 : 256;
+  } else if (lp && g.K > 64 && cdiv64(p.P, 256) * cdiv(g.K, 128) >= 2 * wdno_num_cus()) {
+    // single-plane (bf16) mode has a third of the MFMA work per operand byte: with >= 128 output channels and enough tiles, 256 x 128
+    // tiles (64 x 128 per wave: 6 fragment reads per 8 MFMAs, 41 KB per stage)
+    bm = 256; bn = 128;
+  } else if (shape == 0 && tsplit > 1 && !lp) c.sp = 1;
+  const int64_t nt = cdiv64(p.P, bm) * cdiv(g.K, bn);
+  const int64_t x_elems = (int64_t)g.N * g.D * g.H * g.W * g.C;
+  const int64_t w_elems = (int64_t)g.kd * g.kh * g.K * p.R;
+  if (nt > 0x7fffffff || x_elems * 2 >= T_OOB || w_elems * 2 >= T_OOB || p.P >= 0x7fffffff - bm) return WDNO_EUNSUPPORTED;
+  c.plan.bm = bm; c.plan.bn = bn;
+  c.plan.uniform = 1;
+  c.plan.ksplit = 1;
+  c.plan.tsplit = c.sp ? tsplit : 1;
+  c.plan.ntiles = (int)nt;
+  c.plan.grid = conv_persistent_grid(nt * c.plan.tsplit);
+  return WDNO_OK;
+}
+template <bool LP>
+static int fwd_h3t(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
+                   const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st) {
+  const int bm = c.plan.bm, bn = c.plan.bn;
+  if constexpr (!LP) if (c.sp) return launch_h3t<128, 128, 2, 2, 3, 32, false, true>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if constexpr (LP) if (bm == 256 && bn == 128) return launch_h3t<256, 128, 4, 1, 3, 32, true>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 128 && bn == 128) return launch_h3t<128, 128, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 192 && bn == 128) return launch_h3t<192, 128, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 192 && bn == 64) return launch_h3t<192, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 160 && bn == 128) return launch_h3t<160, 128, 1, 4, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 320 && bn == 64) return launch_h3t<320, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 64 && bn == 64) return launch_h3t<64, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);      // few pixels x many channels (Burgers 8 x 8 level)
+  if (bm == 128 && bn == 64) return launch_h3t<128, 64, 2, 2, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  if (bm == 256 && bn == 64) return launch_h3t<256, 64, 4, 1, 3, 32, LP>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+  return WDNO_EINVAL;
+}
+int wdno_conv_fwd_h3_tap(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
+                         const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st) {
+  if (c.kw == 7) {
+    const int ncb = (p.g.C + 15) / 16;
+    if (p.zb_blocks >= ncb) p.zb_blocks = ncb - 1;          // (a tile must keep at least its centre stage: t_live_stages)
+    if (xl == nullptr) return launch_h3t<256, 64, 4, 1, 7, 16, true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, c, st);
+    if (c.plan.bm == 192) return launch_h3t<192, 64, 2, 2, 7, 16, false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
+    return launch_h3t<256, 64, 4, 1, 7, 16, false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
   }
-  if (xl == nullptr && p.g.K > 64 && cdiv64(p.P, 256) * cdiv(p.g.K, 128) >= 2 * wdno_num_cus())
-    return launch_h3t<256, 128, 4, 1, 3, 32, true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
-  if (xl == nullptr) return fwd_h3t<true>(shape, xh, xh, wh, wh, sx, sw, bias, residual, y, p, st);
-  return fwd_h3t<false>(shape, xh, xl, wh, wl, sx, sw, bias, residual, y, p, st);
+  if (xl == nullptr) return fwd_h3t<true>(xh, xh, wh, wh, sx, sw, bias, residual, y, p, c, st);
+  return fwd_h3t<false>(xh, xl, wh, wl, sx, sw, bias, residual, y, p, c, st);
 }

@@ -1101,6 +1101,19 @@ void wdno_wgrad_h3d_plan(const wdno_conv_geom* g, int* bm, int* bn, int* splits,
   *splits = (int)cdiv64(c.P, pps);
 }
 
+// blocks of a persistent weight-gradient launch over `items` work items, and the per-XCD chunk of the grouped item order (0 = round-robin)
+static int wd_grid(int items, int* xcd_chunk) {
+  int grid = wdno_num_cus();
+  if (items < grid) grid = items;
+  *xcd_chunk = 0;
+  if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {          // WDNO_DBG_WGRAD_NO_XCD_GROUPING: round-robin items (the A/B for the XCD grouping)
+    *xcd_chunk = cdiv(items, 8);
+    grid = wdno_num_cus() & ~7;
+    if (8 * *xcd_chunk < grid) grid = 8 * *xcd_chunk;      // every XCD's blocks walk its chunk in whole rounds; spare blocks idle
+  }
+  return grid;
+}
+
 template <int BM, int BN, bool LP>
 static void launch_wd(const void* xh, const void* xl, const void* dyh, const void* dyl, const float* sx, const float* sdy,
                       const void* table, float* wsf, const WgradDP& w, hipStream_t st) {
@@ -1112,15 +1125,8 @@ static void launch_wd(const void* xh, const void* xl, const void* dyh, const voi
   const size_t lds = (size_t)NS * (LP ? 1 : 2) * (32 * (BM / 8) * 16 + 32 * (BN / 8) * 16);
   static bool done = false;
   if (!done) { (void)hipFuncSetAttribute((const void*)conv_wgrad_h3d_kernel<BM, BN, NS, LP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
-  int grid = wdno_num_cus();
-  if (w.items < grid) grid = w.items;
   WgradDP wl = w;
-  wl.xcd_chunk = 0;
-  if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {          // WDNO_DBG_WGRAD_NO_XCD_GROUPING: round-robin items (the A/B for the XCD grouping)
-    wl.xcd_chunk = cdiv(w.items, 8);
-    grid = wdno_num_cus() & ~7;
-    if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;      // every XCD's blocks walk its chunk in whole rounds; spare blocks idle
-  }
+  const int grid = wd_grid(w.items, &wl.xcd_chunk);
   conv_wgrad_h3d_kernel<BM, BN, NS, LP><<<grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)dyh, (const _Float16*)dyl,
                                                          sx, sdy, (const int4v*)table, wsf, wl, x_bytes, dy_bytes, tbl_bytes);
 }
@@ -1136,15 +1142,8 @@ static void launch_ww(const void* xh, const void* xl, const void* dyh, const voi
   const size_t lds = (size_t)NS * (LP ? 1 : 2) * (2 * 4096 + 2 * 5120);      // two dy tiles + two windows per plane set and stage
   static bool done = false;
   if (!done) { (void)hipFuncSetAttribute((const void*)conv_wgrad_h3w_kernel<NS, LP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
-  int grid = wdno_num_cus();
-  if (w.items < grid) grid = w.items;
   WgradDP wl = w;
-  wl.xcd_chunk = 0;
-  if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {
-    wl.xcd_chunk = cdiv(w.items, 8);
-    grid = wdno_num_cus() & ~7;
-    if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;
-  }
+  const int grid = wd_grid(w.items, &wl.xcd_chunk);
   conv_wgrad_h3w_kernel<NS, LP><<<grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)dyh, (const _Float16*)dyl,
                                                        sx, sdy, (const int4v*)table, wsf, wl, x_bytes, dy_bytes, tbl_bytes);
 }
@@ -1156,26 +1155,15 @@ static void launch_ws(const void* xh, const void* xl, const void* dyh, const voi
   const unsigned x_bytes = (unsigned)((int64_t)g.N * g.D * g.H * g.W * g.C * 2);
   const unsigned dy_bytes = (unsigned)((int64_t)g.N * g.YD * g.YH * g.YW * g.K * 2);
   const size_t lds = (size_t)WDNO_H3S_STAGES * (LP ? 1 : 2) * (4096 + 4096);
-  int grid = wdno_num_cus();
-  if (w.items < grid) grid = w.items;
   WgradDP wl = w;
-  wl.xcd_chunk = 0;
-  if (grid >= 64 && wdno_debug_mode != WDNO_DBG_WGRAD_NO_XCD_GROUPING) {
-    wl.xcd_chunk = cdiv(w.items, 8);
-    grid = wdno_num_cus() & ~7;
-    if (8 * wl.xcd_chunk < grid) grid = 8 * wl.xcd_chunk;
-  }
+  const int grid = wd_grid(w.items, &wl.xcd_chunk);
   conv_wgrad_h3s_kernel<LP><<<grid, 512, lds, st>>>((const _Float16*)xh, (const _Float16*)xl, (const _Float16*)dyh, (const _Float16*)dyl,
                                                    sx, sdy, wsf, wl, x_bytes, dy_bytes);
 }
 
-// wsf: split workspace [splits][ntap][K][R] (or dwp itself when splits == 1). Returns WDNO_EUNSUPPORTED for geometries the
-// DMA kernel does not take.
-int wdno_conv_wgrad_h3_dma(const void* xh, const void* xl, const void* dyh, const void* dyl, const float* sx, const float* sdy,
-                           const void* table, float* wsf, const wdno_conv_geom* g, hipStream_t st) {
-  WgradDP w;
+// The DMA kernels' choice for a geometry: family (WDNO_WGRAD_*), tiles, split plan and item count. WDNO_EUNSUPPORTED for what they do not take.
+static int wd_choose(const wdno_conv_geom* g, WgradDP& w, int& bm, int& bn, int& family) {
   fill_params(w.c, g);
-  int bm, bn;
   wdno_wgrad_h3d_plan(g, &bm, &bn, &w.splits, &w.pix_per_split, &w.splitpair);
   w.n_a = 0x7fffffff;
   if (w.c.P * 16 >= WD_OOB) return WDNO_EUNSUPPORTED;
@@ -1183,20 +1171,46 @@ int wdno_conv_wgrad_h3_dma(const void* xh, const void* xl, const void* dyh, cons
   w.tiles_r = cdiv(w.c.R, bn);
   w.nsteps = w.pix_per_split / 32;
   w.items = w.tiles_k * w.tiles_r * g->kd * g->kh * w.splits;
+  family = WDNO_WGRAD_CHUNKED_H3D;
   if (wd_stem_takes(g)) {
     if ((int64_t)g->N * g->D * g->H * g->W * g->C * 2 >= WD_OOB || w.c.P * g->K * 2 >= WD_OOB) return WDNO_EUNSUPPORTED;
     w.tiles_k = w.tiles_r = 1;
     w.items = g->kd * g->kh * w.splits;
-    if (xl == nullptr) launch_ws<true>(xh, xh, dyh, dyh, sx, sdy, wsf, w, st);
-    else launch_ws<false>(xh, xl, dyh, dyl, sx, sdy, wsf, w, st);
-    return WDNO_OK;
-  }
-  if (wd_window_takes(g)) {      // tiles_r = C / 64 channel tiles, tap rows in pairs
+    family = WDNO_WGRAD_STEM_H3S;
+  } else if (wd_window_takes(g)) {      // tiles_r = C / 64 channel tiles, tap rows in pairs
     w.items = w.tiles_k * w.tiles_r * ((g->kd * g->kh + 1) / 2) * w.splits;
     if (w.splitpair) {           // ordinary items of the even tap rows, then the last tap row over pairs of splits
       w.n_a = w.tiles_k * w.tiles_r * ((g->kd * g->kh) / 2) * w.splits;
       w.items = w.n_a + w.tiles_k * w.tiles_r * ((w.splits + 1) / 2);
     }
+    family = WDNO_WGRAD_WINDOW_H3W;
+  }
+  return WDNO_OK;
+}
+int wdno_wgrad_h3d_describe(const wdno_conv_geom* g, wdno_wgrad_plan* out) {
+  WgradDP w;
+  int bm, bn, family, chunk;
+  int rc = wd_choose(g, w, bm, bn, family);
+  if (rc) return rc;
+  out->family = family; out->bm = bm; out->bn = bn;
+  out->splits = w.splits; out->pix_per_split = w.pix_per_split; out->splitpair = w.splitpair;
+  out->items = w.items; out->grid = wd_grid(w.items, &chunk);
+  return WDNO_OK;
+}
+// wsf: split workspace [splits][ntap][K][R] (or dwp itself when splits == 1). Returns WDNO_EUNSUPPORTED for geometries the
+// DMA kernel does not take.
+int wdno_conv_wgrad_h3_dma(const void* xh, const void* xl, const void* dyh, const void* dyl, const float* sx, const float* sdy,
+                           const void* table, float* wsf, const wdno_conv_geom* g, hipStream_t st) {
+  WgradDP w;
+  int bm, bn, family;
+  int rc = wd_choose(g, w, bm, bn, family);
+  if (rc) return rc;
+  if (family == WDNO_WGRAD_STEM_H3S) {
+    if (xl == nullptr) launch_ws<true>(xh, xh, dyh, dyh, sx, sdy, wsf, w, st);
+    else launch_ws<false>(xh, xl, dyh, dyl, sx, sdy, wsf, w, st);
+    return WDNO_OK;
+  }
+  if (family == WDNO_WGRAD_WINDOW_H3W) {
     if (xl == nullptr) launch_ww<true>(xh, xh, dyh, dyh, sx, sdy, table, wsf, w, st);
     else launch_ww<false>(xh, xl, dyh, dyl, sx, sdy, table, wsf, w, st);
     return WDNO_OK;

@@ -783,6 +783,15 @@ def conv_fwd_h3(planes, shape4, w, pack, kind, bias_p, residual, ks, st, pd, kp,
     flops = 2.0 * n * osp[0] * osp[1] * osp[2] * kp * ks[0] * ks[1] * ks[2] * cp8
     tap = (out is None and tuple(st) == (1, 1, 1) and tuple(osp) == (d, h, ww) and max(ks) <= 8 and      # csrc/conv_h3t.hip: wdno_conv_h3t_takes
            ((ks[2] == 3 and cp8 % 32 == 0) or (ks[2] == 7 and cp8 % 16 == 0 and kp <= 64)))
+    # layers of few pixels x many channels lend the library a workspace for the partial sums of a split reduction (csrc/conv_h3t.hip)
+    wsb = 0
+    if xl is not None and tap and ks[2] == 3:
+        key = (n, d, h, ww, cp8, kp, tuple(ks), tuple(osp))
+        wsb = _split_ws_bytes.get(key)
+        if wsb is None:
+            wsb = _split_ws_bytes[key] = int(_lib_().wdno_conv_fwd_split_ws_bytes(C.byref(g)))
+    if LAUNCH_LOG is not None:
+        LAUNCH_LOG.append(('fwd', _geom_fields(g), xl is None, residual is not None, wsb))
     with _timed(_fwd_h3_kernel_name(n * osp[0] * osp[1] * osp[2], kp, ks, tap, cp8 if xl is not None else None), flops):
         zb = None
         if zero_box is not None and tap and ks[2] == 7:      # the 7-wide stem skips the reduction stages that only see the caller's zeros (csrc/conv_h3t.hip)
@@ -798,13 +807,6 @@ def conv_fwd_h3(planes, shape4, w, pack, kind, bias_p, residual, ks, st, pd, kp,
             _lib.check(_lib_().wdno_conv_fwd_f16x3_zbox(_p(xh), _p(xl), _p(sx), _p(wh), _p(wl), _p(sw), _p(bias_p), _p(residual), _p(y),
                                                         _p(amax_rec), C.byref(g), C.byref(zb), _stream()), 'conv_fwd_f16x3_zbox')
             return y
-        # layers of few pixels x many channels lend the library a workspace for the partial sums of a split reduction (csrc/conv_h3t.hip)
-        key = (n, d, h, ww, cp8, kp, tuple(ks), tuple(osp)) if tap and ks[2] == 3 else None
-        wsb = 0
-        if key is not None:
-            wsb = _split_ws_bytes.get(key)
-            if wsb is None:
-                wsb = _split_ws_bytes[key] = int(_lib_().wdno_conv_fwd_split_ws_bytes(C.byref(g)))
         if wsb:
             ws = torch.empty(wsb // 4, device=xh.device, dtype=torch.float32)
             _lib.check(_lib_().wdno_conv_fwd_f16x3_ws(_p(xh), _p(xl), _p(sx), _p(wh), _p(wl), _p(sw), _p(bias_p), _p(residual), _p(y),
@@ -819,6 +821,30 @@ _split_ws_bytes = {}
 
 
 _pixel_tables = {}
+
+
+LAUNCH_LOG = None         # tests set this to a list: ('fwd' | 'wgrad', geometry fields, ...) of every split-kernel launch below, for the plan queries
+
+
+def _geom_fields(g):
+    return tuple(getattr(g, k) for k, _ in _lib.ConvGeom._fields_)
+
+
+def conv_fwd_plan(g, lowp=False, residual_is_y=False, split_ws_bytes=0):
+    """What wdno_conv_fwd_f16x3* / _bf16* would launch for geometry g (lowp None: what wdno_conv_fwd would), as the library's own
+    launch path decides it: _lib.ConvPlan (family is an index into _lib.CONV_FAMILIES). residual_is_y: the residual would be y itself.
+    No launch, no device needed."""
+    pl = _lib.ConvPlan()
+    _lib.check(_lib_().wdno_conv_fwd_plan(C.byref(g), -1 if lowp is None else int(bool(lowp)), int(bool(residual_is_y)), int(split_ws_bytes),
+                                          C.byref(pl)), 'conv_fwd_plan')
+    return pl
+
+
+def conv_wgrad_plan(g, lowp=False, kn=0, cn=0):
+    """Same for the weight gradient (wdno_conv_wgrad_f16x3_param / _partials / _bf16_param with the parameter extents kn, cn): _lib.ConvWgradPlan."""
+    pl = _lib.ConvWgradPlan()
+    _lib.check(_lib_().wdno_conv_wgrad_plan(C.byref(g), int(bool(lowp)), int(kn), int(cn), C.byref(pl)), 'conv_wgrad_plan')
+    return pl
 
 
 def _fwd_h3_kernel_name(pixels, k, ks, tap=False, c=None):
@@ -994,6 +1020,8 @@ def conv_wgrad_h3(xplanes, shape4, gyplanes, osp, ks, st, pd, param_kc=None, out
         _lib.check(lib.wdno_conv_pixel_table(_p(table), C.byref(g), _stream()), 'conv_pixel_table')
         _pixel_tables[tkey] = table
     flops = 2.0 * n * osp[0] * osp[1] * osp[2] * k8 * ks[0] * ks[1] * ks[2] * c8
+    if LAUNCH_LOG is not None:
+        LAUNCH_LOG.append(('wgrad', _geom_fields(g), xl is None, param_kc))
     window = tuple(st) == (1, 1, 1) and tuple(osp) == (d, h, ww) and ks[2] == 3 and pd[2] == 1 and c8 % 64 == 0
     if tuple(st) == (1, 1, 1) and tuple(osp) == (d, h, ww) and ks[2] == 7 and pd[2] == 3 and c8 == 48 and k8 <= 64 and max(ks) <= 8:
         window = 'stem'                    # csrc/conv_wgrad_h3d.hip: wd_stem_takes
