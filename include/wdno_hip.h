@@ -471,6 +471,11 @@ int wdno_tattn_fused_bwd(const float* x, const float* dy, const float* gamma, fl
                          const float* rot_sin, const float* bias, const float* rec_dy, const float* rec_v, float* dx, float* amax_rec,
                          float* grads, void* ws, size_t ws_bytes,
                          int64_t n_batch, int n_tok, int64_t hw, int C, int heads, float scale, wdno_stream_t s);
+/* The grids those two calls launch for a shape (no device work; the tests' case matrices ask it which regime a shape reaches). Blocks walk the
+ * n_batch * hw sequences with a stride of the grid: ceil(n_batch * hw / grid) passes, the sample advancing by grid / hw and the pixel by
+ * grid % hw per step. grid_bwd = 0 where there is no fused backward (48 frames, 128 / 256 channels). WDNO_EUNSUPPORTED for shapes
+ * wdno_tattn_fused_takes refuses. */
+int wdno_tattn_fused_plan(int C, int n_tok, int64_t n_batch, int64_t hw, int* grid_fwd, int* grid_bwd);
 
 /* The SpatialLinearAttention block of the 64-channel levels FORWARD, for passes that need no gradient (csrc/linattn_fused.hip): replaces
  * Residual(PreNorm(dim, SpatialLinearAttention(dim, heads))) -- smoke/video_diffusion_pytorch/video_diffusion_pytorch_conv3d.py:165-174
@@ -497,6 +502,11 @@ int wdno_lattn_fused_bwd(const float* x, const float* dy, const float* gamma, fl
                          const float* wq_scale, const void* wot_hi, const void* wot_lo, const float* wot_scale, const float* ctx,
                          const float* kstat, const float* rec_dy, float* dx, float* amax_rec, float* grads, void* ws, size_t ws_bytes,
                          int64_t units, int n_tok, int C, int heads, float scale, wdno_stream_t s);
+/* The cuts wdno_lattn_fused_fwd / wdno_lattn_fused_bwd make for a shape (no device work): a frame's ceil(n_tok / 32) token tiles go to `chunks`
+ * chunks of `tiles_per_chunk` tiles (forward passes and the backward's reduction pass, one block per (frame, chunk); trailing chunks may be
+ * short or empty); the backward's last pass cuts them into `chunks2` of `tiles_per_chunk2` and runs the units * chunks2 items on `grid2`
+ * persistent blocks -- also the number of partials its ordered reduction sums. */
+int wdno_lattn_fused_plan(int64_t units, int n_tok, int* chunks, int* tiles_per_chunk, int* chunks2, int* tiles_per_chunk2, int* grid2);
 
 /* relative-position bias of the temporal attention (conv3d.py:74-112): bias[h][i][j] = W[bucket[i][j]][h] with W [num_buckets, heads]
  * (nn.Embedding weight) and bucket [n, n] int64 (host-built integer table); and dW from d(bias). One launch each. */

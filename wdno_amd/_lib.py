@@ -195,6 +195,8 @@ PROTOTYPES = {
     'wdno_lattn_fused_bwd_grads': (I, []),
     'wdno_lattn_fused_bwd_ws_bytes': (Z, [L, I]),
     'wdno_lattn_fused_bwd': (I, [P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, Z, L, I, I, I, F, P]),
+    'wdno_tattn_fused_plan': (I, [I, I, L, L, C.POINTER(I), C.POINTER(I)]),
+    'wdno_lattn_fused_plan': (I, [L, I, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
     'wdno_tattn_fused_bwd_ws_bytes': (Z, []),
     'wdno_tattn_fused_bwd_grads': (I, []),
     'wdno_tattn_fused_bwd': (I, [P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, Z, L, I, L, I, I, F, P]),

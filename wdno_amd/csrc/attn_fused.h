@@ -406,3 +406,14 @@ struct TFusedP {
   float* rec_v;                                                             // optional amax record of v (attn_fused_bwd.hip: the plane scale of the attention output)
   int HW; float scale; int64_t nseq;
 };
+
+// blocks per CU of the four temporal kernels' persistent grids, and the grid itself (at most one block per sequence): what the launchers
+// launch and what wdno_tattn_fused_plan (attn_fused.hip) answers
+#define TF_BPC_FWD 2       /* attn_fused.hip */
+#define TF_BPC_FWD48 1     /* attn_fused48.hip */
+#define TF_BPC_WIDE 2      /* attn_fused_wide.hip */
+#define TF_BPC_BWD 1       /* attn_fused_bwd.hip */
+static inline int64_t tf_grid(int blocks_per_cu, int64_t nseq) {
+  const int64_t grid = blocks_per_cu * (int64_t)wdno_num_cus();
+  return grid > nseq ? nseq : grid;
+}

@@ -180,8 +180,18 @@ extern "C" int wdno_tattn_fused_fwd(const float* x, const float* gamma, float ep
     if (qkv_out) return WDNO_EUNSUPPORTED;          // (only the un-fused backward of the 24-frame block asks for the projections)
     return wdno_tattn_fused_fwd48_launch(p, as_stream(s));
   }
-  int64_t grid = 2 * (int64_t)wdno_num_cus();
-  if (grid > p.nseq) grid = p.nseq;
+  const int64_t grid = tf_grid(TF_BPC_FWD, p.nseq);
   tattn_fused_fwd_kernel<<<(int)grid, 256, 0, as_stream(s)>>>(p);
   return wdno_check_launch();
+}
+
+// the grids wdno_tattn_fused_fwd / wdno_tattn_fused_bwd launch for this shape (0: no such kernel). Blocks walk the n_batch * hw sequences
+// with a stride of the grid: passes = ceil(nseq / grid), per step the sample advances by grid / hw and the pixel by grid % hw (with a carry).
+extern "C" int wdno_tattn_fused_plan(int C, int n_tok, int64_t n_batch, int64_t hw, int* grid_fwd, int* grid_bwd) {
+  WDNO_REQUIRE(grid_fwd && grid_bwd && n_batch > 0 && hw > 0);
+  if (!wdno_tattn_fused_takes(C, n_tok, TF_HEADS)) return WDNO_EUNSUPPORTED;
+  const int64_t nseq = n_batch * hw;
+  *grid_fwd = (int)tf_grid(C != TF_C ? TF_BPC_WIDE : n_tok == 48 ? TF_BPC_FWD48 : TF_BPC_FWD, nseq);
+  *grid_bwd = C == TF_C && n_tok == TF_NT ? (int)tf_grid(TF_BPC_BWD, nseq) : 0;
+  return WDNO_OK;
 }

@@ -206,8 +206,7 @@ int wdno_tattn_fused_fwd48_launch(const TFusedP& p, hipStream_t st) {
     if (hipFuncSetAttribute((const void*)tattn_fused_fwd48_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T48_LDS_BYTES) != hipSuccess) return WDNO_ELAUNCH;
     attr_done = true;
   }
-  int64_t grid = wdno_num_cus();
-  if (grid > p.nseq) grid = p.nseq;
+  const int64_t grid = tf_grid(TF_BPC_FWD48, p.nseq);
   tattn_fused_fwd48_kernel<<<(int)grid, 512, T48_LDS_BYTES, st>>>(p);
   return wdno_check_launch();
 }

@@ -505,8 +505,7 @@ extern "C" int wdno_tattn_fused_bwd(const float* x, const float* dy, const float
 #endif
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS_BYTES) != hipSuccess) return WDNO_ELAUNCH;
   }
-  int64_t grid = wdno_num_cus();
-  if (grid > p.nseq) grid = p.nseq;
+  const int64_t grid = tf_grid(TF_BPC_BWD, p.nseq);
   kern<<<(int)grid, 256, TB_LDS_BYTES, as_stream(s)>>>(p);
   int rc = wdno_check_launch();
   if (rc) return rc;

@@ -230,8 +230,7 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
 
 // C = 128 / 256, 24 frames, forward only (attn_fused.hip routes here; qkv_out / rec_v are not produced)
 int wdno_tattn_fused_fwd_wide_launch(const TFusedP& p, int C, hipStream_t st) {
-  int64_t grid = 2 * (int64_t)wdno_num_cus();
-  if (grid > p.nseq) grid = p.nseq;
+  const int64_t grid = tf_grid(TF_BPC_WIDE, p.nseq);
   if (C == 128) tattn_wide_fwd_kernel<128><<<(int)grid, 256, 0, st>>>(p);
   else if (C == 256) tattn_wide_fwd_kernel<256><<<(int)grid, 256, 0, st>>>(p);
   else return WDNO_EUNSUPPORTED;

@@ -27,3 +27,8 @@ static inline int lf_chunks(int64_t units, int n_tok) {
   if (c > 64) c = 64;
   return (int)c;
 }
+// tiles (32 tokens) a chunk walks when a frame is cut into `chunks`: trailing chunks may be short or empty
+static inline int lf_tiles_per_chunk(int n_tok, int chunks) {
+  const int ntiles = (n_tok + 31) / 32;
+  return (ntiles + chunks - 1) / chunks;
+}

@@ -264,8 +264,7 @@ extern "C" int wdno_lattn_fused_fwd(const float* x, const float* gamma, float ep
   p.wo_hi = (const _Float16*)wo_hi; p.wo_lo = (const _Float16*)wo_lo; p.wo_scale = wo_scale;
   p.bias_out = bias_out;
   p.n_tok = n_tok; p.chunks = lf_chunks(units, n_tok);
-  const int ntiles = (n_tok + 31) / 32;
-  p.tiles_per_chunk = (ntiles + p.chunks - 1) / p.chunks;
+  p.tiles_per_chunk = lf_tiles_per_chunk(n_tok, p.chunks);
   p.scale = scale;
   p.part = (float*)ws;
   float* ctx = ctx_out ? ctx_out : (float*)ws + (size_t)units * p.chunks * TF_HEADS * LF_PART;

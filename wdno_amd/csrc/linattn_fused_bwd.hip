@@ -498,6 +498,25 @@ static int lb_chunks2(int64_t units, int n_tok, int64_t grid) {
   }
   return best;
 }
+// the persistent grid of pass 2: one block per CU, at most one per (frame, chunk) item
+static int64_t lb_grid2(int64_t units, int chunks2) {
+  const int64_t nitems2 = units * chunks2;
+  int64_t grid = wdno_num_cus();
+  if (grid > nitems2) grid = nitems2;
+  return grid;
+}
+// the cuts the launches make for this shape: `chunks` of `tiles_per_chunk` tiles per frame in the forward passes and the backward's first
+// pass (grid units * chunks), `chunks2` of `tiles_per_chunk2` in the backward's second pass on a grid of `grid2` blocks (a block takes the
+// items blockIdx, blockIdx + grid2, ...; grid2 is also the number of partials lattn_fused_reduce_kernel sums)
+extern "C" int wdno_lattn_fused_plan(int64_t units, int n_tok, int* chunks, int* tiles_per_chunk, int* chunks2, int* tiles_per_chunk2, int* grid2) {
+  WDNO_REQUIRE(units > 0 && n_tok > 0 && chunks && tiles_per_chunk && chunks2 && tiles_per_chunk2 && grid2);
+  *chunks = lf_chunks(units, n_tok);
+  *tiles_per_chunk = lf_tiles_per_chunk(n_tok, *chunks);
+  *chunks2 = lb_chunks2(units, n_tok, wdno_num_cus());
+  *tiles_per_chunk2 = lf_tiles_per_chunk(n_tok, *chunks2);
+  *grid2 = (int)lb_grid2(units, *chunks2);
+  return WDNO_OK;
+}
 extern "C" int wdno_lattn_fused_bwd_grads(void) { return LB_E; }
 extern "C" size_t wdno_lattn_fused_bwd_ws_bytes(int64_t units, int n_tok) {
   return ((size_t)units * lf_chunks(units, n_tok) * TF_HEADS * 1024 + (size_t)units * TF_HEADS * (1024 + 32) + (size_t)wdno_num_cus() * LB_E) * sizeof(float);
@@ -516,8 +535,7 @@ extern "C" int wdno_lattn_fused_bwd(const float* x, const float* dy, const float
   p.wo_hi = (const _Float16*)wot_hi; p.wo_lo = (const _Float16*)wot_lo; p.wo_scale = wot_scale;
   p.ctx = ctx; p.kstat = kstat; p.rec_dy = rec_dy;
   p.n_tok = n_tok; p.chunks = lf_chunks(units, n_tok); p.units = units; p.scale = scale;
-  const int ntiles = (n_tok + 31) / 32;
-  p.tiles_per_chunk = (ntiles + p.chunks - 1) / p.chunks;
+  p.tiles_per_chunk = lf_tiles_per_chunk(n_tok, p.chunks);
   float* w = (float*)ws;
   p.part1 = w; w += (size_t)units * p.chunks * TF_HEADS * 1024;
   p.dctx = w; w += (size_t)units * TF_HEADS * 1024;
@@ -527,8 +545,7 @@ extern "C" int wdno_lattn_fused_bwd(const float* x, const float* dy, const float
   const int64_t nitems = units * p.chunks;
   if (nitems > 0x7fffffff) return WDNO_EUNSUPPORTED;
   p.chunks2 = lb_chunks2(units, n_tok, wdno_num_cus());
-  p.tiles_per_chunk2 = (ntiles + p.chunks2 - 1) / p.chunks2;
-  const int64_t nitems2 = units * p.chunks2;
+  p.tiles_per_chunk2 = lf_tiles_per_chunk(n_tok, p.chunks2);
   static bool attr_done = false;
   if (!attr_done) {
     if (hipFuncSetAttribute((const void*)lattn_fused_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LB_LDS_BYTES) != hipSuccess) return WDNO_ELAUNCH;
@@ -537,8 +554,7 @@ extern "C" int wdno_lattn_fused_bwd(const float* x, const float* dy, const float
   hipStream_t st = as_stream(s);
   lattn_fused_dctx_kernel<<<(unsigned)nitems, 256, 0, st>>>(p);
   lattn_fused_dctx_merge_kernel<<<(unsigned)(units * TF_HEADS), 256, 0, st>>>(p.part1, ctx, p.dctx, p.tvec, p.chunks);
-  int64_t grid = wdno_num_cus();
-  if (grid > nitems2) grid = nitems2;
+  const int64_t grid = lb_grid2(units, p.chunks2);
   lattn_fused_bwd_kernel<<<(unsigned)grid, 256, LB_LDS_BYTES, st>>>(p);
   lattn_fused_reduce_kernel<<<(LB_E + 31) / 32, 256, 0, st>>>(p.part2, (int)grid, grads, LB_E);
   return wdno_check_launch();

@@ -2221,6 +2221,30 @@ def linear_attention_fused(x, gamma, eps, w_qkv, w_out, b_out, heads, scale):
     return _LAttnFused.apply(x, gamma, w_qkv, w_out, b_out, eps, heads, scale)
 
 
+def tattn_fused_plan(c, frames, batch, hw):
+    """The grids the fused temporal attention launches for CL [batch, frames, H, W, c] with hw = H W, as the library's launch path decides
+    them: dict(nseq, grid_fwd, grid_bwd) and, per direction d, passes_d / gstep_b_d / gstep_p_d (the walk of csrc/attn_fused.hip: sample and
+    pixel steps of a block from one sequence to its next). grid_bwd = 0: no fused backward. No launch, no device needed."""
+    gf, gb = C.c_int(0), C.c_int(0)
+    _lib.check(_lib_().wdno_tattn_fused_plan(int(c), int(frames), int(batch), int(hw), C.byref(gf), C.byref(gb)), 'tattn_fused_plan')
+    nseq = batch * hw
+    out = {'nseq': nseq, 'grid_fwd': gf.value, 'grid_bwd': gb.value}
+    for d, g in (('fwd', gf.value), ('bwd', gb.value)):
+        if g:
+            out.update({'passes_' + d: -(-nseq // g), 'gstep_b_' + d: g // hw, 'gstep_p_' + d: g % hw})
+    return out
+
+
+def lattn_fused_plan(units, n_tok):
+    """The cuts the fused linear attention makes for `units` frames of n_tok tokens (csrc/linattn_fused.hip, linattn_fused_bwd.hip):
+    dict(ntiles, chunks, tiles_per_chunk, chunks2, tiles_per_chunk2, grid2). No launch, no device needed."""
+    v = [C.c_int(0) for _ in range(5)]
+    _lib.check(_lib_().wdno_lattn_fused_plan(int(units), int(n_tok), *[C.byref(t) for t in v]), 'lattn_fused_plan')
+    out = dict(zip(('chunks', 'tiles_per_chunk', 'chunks2', 'tiles_per_chunk2', 'grid2'), (t.value for t in v)))
+    out['ntiles'] = (n_tok + 31) // 32
+    return out
+
+
 class _RelPosBias(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, bucket):
