@@ -823,6 +823,52 @@ typedef struct {
 } wdno_smoke_score_channel;
 int wdno_smoke_score(const float* pred, const wdno_smoke_score_channel* data, double* out, int B, int T, int h, int w, wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ Burgers evaluation: reconstruction and scoring
+ * wdno_burgers_reconstruct: the wavelet branch of diffuse_2dconv (eval_ddpm_burgers.py:185-195) for the whole batch in one launch. For the
+ * sampled state x [B][C][H][W] in network units (C >= 8, strides in elements, columns contiguous), rescaler [>= 8], the coefficient block
+ * (h, w) and the field size (n_t, n_x), with the coefficients read in place and x RESCALER formed on the fly:
+ *   u_f = IDWT2((x RESCALER)[:, 0:8, :h, :w])[:, :, :n_t, :n_x]   (channels 0-3 = LL, da, ad, dd of u, 4-7 of f; H pass, then W pass;
+ *                                                                   periodization, L = 10: an axis of v coefficients gives 2 v samples)
+ *   u = u_f[:, 0]  [B][n_t][n_x],   f = u_f[:, 1, :n_t - 1]  [B][n_t - 1][n_x],   fp32, contiguous, each written once.
+ * Nothing outside the block is read. A workgroup per (sample, field, tile of tn reconstruction rows, full width) runs both passes with its
+ * intermediates in lds_bytes of LDS (8 tn w bytes); the arithmetic and its order are those of wdno_burgers_guidance's residual. Nothing is
+ * allocated; no atomics, every sum in a fixed order: a sample's bits do not depend on B or its index. x, u and f must not overlap. tn even,
+ * (ntile - 1) tn < n_t <= ntile tn, lds_bytes <= 64 KiB (wdno_amd/burgers/reconstruct.py: plan). filt as for wdno_burgers_guidance.
+ * WDNO_EUNSUPPORTED for anything but mode 0 (periodization) with L = 10 (bior2.4); WDNO_EINVAL for inconsistent integers: a block larger
+ * than the tensor, a crop larger than the reconstruction, an LDS size or strides that do not fit. Nothing is written then. */
+typedef struct {
+  int B, C, H, W;                                  /* the tensor x */
+  long long sample_stride;                         /* in elements; columns are contiguous */
+  int chan_stride, row_stride;
+  int h, w, n_t, n_x;                              /* coefficient block (padded_shape) and field size (ori_shape): n_t <= 2h, n_x <= 2w */
+  int L, mode;
+  int tn, ntile, lds_bytes, reserved;
+} wdno_burgers_reconstruct_desc;
+int wdno_burgers_reconstruct(const float* x, const float* rescaler, float* u, float* f, const wdno_burgers_reconstruct_desc* d,
+                             const float* filt, wdno_stream_t s);
+
+/* wdno_burgers_score: the sums and order statistics behind mse_deviation and the two metric(..., evaluate=True) calls of diffuse_2dconv
+ * (eval_ddpm_burgers.py:220-230, test_util.py:79-98) for one batch in one launch, one workgroup per sample. u [B][n_t][n_x] and
+ * f [B][n_t - 1][n_x] fp32 contiguous (as wdno_burgers_reconstruct writes them); x_gt and u_target fp32 views of [B][n_t][n_x sub]:
+ * element (b, r, c) at ptr[b sample_stride + r row_stride + c col_stride], strides in elements, >= 0. With t = u_target[b, n_t - 1, :],
+ * the candidates c0 = u[b, n_t - 1] with every value repeated sub times and c1 = x_gt[b, n_t - 1, :], every difference formed as
+ * (double)a - (double)b and accumulated in fp64, out [B][14] fp64:
+ *   out[b][0]           sum over rows 1 .. n_t - 1 and columns j of (u[b, r, j] - x_gt[b, r, j sub])^2
+ *   out[b][1 + 5 k ..]  for candidate k: sum (c - t)^2 over the columns ::sub | sum (c - t)^2 | sum |c - t| | lower median of (c - t)^2 |
+ *                       lower median of |c - t|   (the element of rank (n - 1) / 2 of the sorted row, torch's median; exact selection)
+ *   out[b][11]          sum f^2        out[b][12] sum t^2        out[b][13] sum |t|
+ * lds_bytes = 16 n_x sub (the two fp64 rows the medians are selected from), n_x sub <= 3840. No atomics, a fixed order: a sample's row
+ * does not depend on B or its index. Nothing is allocated. WDNO_EINVAL for inconsistent integers, negative strides or misaligned
+ * pointers. */
+typedef struct {
+  int B, n_t, n_x, sub;
+  long long gt_sample_stride, gt_row_stride, gt_col_stride;      /* x_gt */
+  long long ut_sample_stride, ut_row_stride, ut_col_stride;      /* u_target */
+  int lds_bytes, reserved;
+} wdno_burgers_score_desc;
+int wdno_burgers_score(const float* u, const float* f, const float* x_gt, const float* u_target, double* out,
+                       const wdno_burgers_score_desc* d, wdno_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

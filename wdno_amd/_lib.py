@@ -98,6 +98,17 @@ class SmokeScoreChannel(C.Structure):       # include/wdno_hip.h: wdno_smoke_sco
                [('is_double', I), ('reserved', I)]
 
 
+class BurgersReconstructDesc(C.Structure):  # include/wdno_hip.h: wdno_burgers_reconstruct_desc
+    _fields_ = [(k, I) for k in ('B', 'C', 'H', 'W')] + [('sample_stride', C.c_longlong)] + \
+               [(k, I) for k in ('chan_stride', 'row_stride', 'h', 'w', 'n_t', 'n_x', 'L', 'mode', 'tn', 'ntile', 'lds_bytes', 'reserved')]
+
+
+class BurgersScoreDesc(C.Structure):        # include/wdno_hip.h: wdno_burgers_score_desc
+    _fields_ = [(k, I) for k in ('B', 'n_t', 'n_x', 'sub')] + \
+               [(k, C.c_longlong) for k in ('gt_sample_stride', 'gt_row_stride', 'gt_col_stride', 'ut_sample_stride', 'ut_row_stride', 'ut_col_stride')] + \
+               [('lds_bytes', I), ('reserved', I)]
+
+
 PD, PG, PA, PC = C.POINTER(DwtDesc), C.POINTER(ConvGeom), C.POINTER(AttnDesc), C.POINTER(CondDesc)
 PF = C.POINTER(C.c_float)
 
@@ -242,6 +253,8 @@ PROTOTYPES = {
     'wdno_smoke_noise': (I, [P, P, P, P, I, C.c_uint64, P, P]),
     'wdno_smoke_reconstruct': (I, [P, P, P, C.POINTER(SmokeReconstructDesc), PF, P]),
     'wdno_smoke_score': (I, [P, C.POINTER(SmokeScoreChannel), P, I, I, I, I, P]),
+    'wdno_burgers_reconstruct': (I, [P, P, P, P, C.POINTER(BurgersReconstructDesc), PF, P]),
+    'wdno_burgers_score': (I, [P, P, P, P, P, C.POINTER(BurgersScoreDesc), P]),
 }
 
 _lib = None
