@@ -374,6 +374,13 @@ int wdno_layernorm_bwd_add(const float* x, const float* g, const float* dy, cons
 /* ... and max|dx| left in an amax record (dx is the dy of the projection in front of the next Residual block). amax_rec may be NULL. */
 int wdno_layernorm_bwd_add_amax(const float* x, const float* g, const float* dy, const float* add_to, float* dx, float* dg, float* amax_rec,
                                 int64_t P, int C, float eps, void* ws, size_t ws_bytes, wdno_stream_t s);
+/* What the LayerNorm launches above do for P rows of C channels (nothing is launched; the launch path asks the same code): a row is held
+ * by tpr lanes with vpl float4 each (lanes past C / 4 are masked), a block of 256 threads takes rows_per_block = 256 / tpr rows at a time
+ * and walks the rows with a stride of blocks * rows_per_block: max_rows_walk = the most rows one row group visits (> 1 beyond 1024
+ * blocks). rc = the code the launch would return: WDNO_EINVAL (P <= 0, C < 4), WDNO_EUNSUPPORTED (C % 4 != 0 or C > 1024; the planes
+ * form also refuses C % 8 != 0). The other fields are 0 when rc != WDNO_OK. Returns WDNO_EINVAL only for out == NULL. */
+typedef struct { int tpr, vpl, rows_per_block, blocks, max_rows_walk, rc; } wdno_ln_plan;
+int wdno_layernorm_plan(int64_t P, int C, wdno_ln_plan* out);
 
 /* ------------------------------------------------------------------------------------------------ attention
  * qkv rows are [row][3*heads*32] = (q | k | v), each [heads][32]; outputs are [row][heads*32].
@@ -388,10 +395,19 @@ typedef struct {
 } wdno_attn_desc;
 int wdno_attn_fwd(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
                   const wdno_attn_desc* d, float scale, wdno_stream_t s);
-/* out = the forward result (saved); dqkv (same layout as qkv); dbias [heads][n][n] (written, not accumulated) or NULL. n_tok <= 128.
+/* out = the forward result (saved); dqkv (same layout as qkv); dbias [heads][n][n] (written, not accumulated) or NULL.
+ * Token limits (WDNO_EUNSUPPORTED beyond; wdno_attn_bwd_plan reports the code without launching): n_tok <= 32 always (matrix kernels);
+ * without rotation, bias and bias gradient n_tok <= 576; with rotation or bias above 32 tokens the thread-per-row kernel keeps K, Q, P and dS
+ * of its items and the bias-gradient partial in LDS, ((2 + heads_if_dbias) n^2 + 66 n + 16) * 4 bytes <= 160 KB at one item per block:
+ * n_tok <= 127 without a bias gradient, and with one n_tok <= 106 / 93 / 77 / 60 at 1 / 2 / 4 / 8 heads. The kernel takes 128 / n_tok items
+ * per block where that fits and fewer where it does not (64 tokens, 4 heads and a bias gradient: one item instead of two).
  * The relative-position-bias gradient is DETERMINISTIC: every block leaves its partial sum in the workspace (wdno_attn_bwd_ws_bytes,
  * needed only when dbias != NULL) and a second launch adds the partials in block order; with heads == 4 and n_tok <= 32 a wave sums
- * its items in registers in item order (no atomics anywhere). */
+ * its items in registers in item order. Inside a block no address of the partial has two writers: the matrix kernel gives every wave a
+ * partial of its own when heads % 4 != 0, the thread-per-row kernel takes at most `heads` items per block when there is a bias gradient.
+ * THE EXCEPTION: up to 32 tokens with heads % 4 != 0 where four partials do not fit the 160 KB of LDS (from 9 heads on at 32 tokens) the waves
+ * share one partial and two of them add to one address in arrival order: dbias may then differ in its last bits between two runs
+ * (wdno_attn_bwd_plan reports dbias_in_lds = 2 for such a launch). */
 size_t wdno_attn_bwd_ws_bytes(const wdno_attn_desc* d);
 int wdno_attn_bwd(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out,
                   const float* dout, float* dqkv, float* dbias, const wdno_attn_desc* d, float scale, void* ws, size_t ws_bytes,
@@ -416,6 +432,22 @@ int wdno_attn_bwd_planes(const float* qkv, const float* rot_cos, const float* ro
 int wdno_attn_fwd_planes(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out, void* out_hi,
                          void* out_lo, float* out_scale, float* amax_rec, const float* rec_qkv, const wdno_attn_desc* d, float scale,
                          wdno_stream_t s);
+/* What wdno_attn_fwd* / wdno_attn_bwd* would launch (nothing is launched; the launch paths ask the same code, so the library debug modes
+ * change the answers as they change the launches). has_rot / has_bias: tables given; want_dbias: dbias != NULL (backward); planes: the
+ * *_planes form. family: WDNO_ATTN_*; grid: blocks; items_per_block: (unit, head) items a block holds at a time (waves of the matrix
+ * kernels, item slots of the thread-per-row ones; tiled forward: (item, query tile) pairs); max_walk: the most items (pairs, item groups)
+ * one wave / block visits with its grid stride; dbias_partials: rows of the workspace the dbias reduce sums (= grid when want_dbias);
+ * dbias_in_lds: LDS arrays [heads][n][n] that hold the block's partial: 0 = registers of its waves (heads == 4 on the matrix kernel), 1 = one
+ * array whose every address has a single writer (the thread-per-row kernel; the matrix kernel with heads a multiple of 4), 4 = one per wave,
+ * added in wave order (the matrix kernel with any other head count), 2 = one array that two waves add to in arrival order (the matrix
+ * kernel where heads % 4 != 0 and four arrays do not fit: not reproducible bit for bit); lds_bytes: dynamic LDS;
+ * rc: the code the launch would return for these arguments, short of WDNO_EWORKSPACE / WDNO_ELAUNCH. Fields other than rc are 0 and family
+ * is WDNO_ATTN_NONE when rc != WDNO_OK. The functions return WDNO_EINVAL only for out == NULL. */
+enum { WDNO_ATTN_NONE = -1, WDNO_ATTN_MFMA24 = 0, WDNO_ATTN_MFMA = 1, WDNO_ATTN_MFMA64 = 2, WDNO_ATTN_TILED = 3, WDNO_ATTN_TILED_STAGED = 4,
+       WDNO_ATTN_TILED_UNSTAGED = 5, WDNO_ATTN_BIG = 6, WDNO_ATTN_ROWS = 7 };
+typedef struct { int family, grid, items_per_block, max_walk, dbias_partials, dbias_in_lds, lds_bytes, rc; } wdno_attn_plan;
+int wdno_attn_fwd_plan(const wdno_attn_desc* d, int has_rot, int has_bias, int want_dbias, int planes, wdno_attn_plan* out);
+int wdno_attn_bwd_plan(const wdno_attn_desc* d, int has_rot, int has_bias, int want_dbias, int planes, wdno_attn_plan* out);
 /* Linear attention (unet.py:203-223 ; conv3d.py:241-258): q softmax over the 32 head channels, k softmax over
  * tokens, ctx = k^T v, out = ctx^T q * scale. units x n_tok rows, contiguous. ws holds k statistics and ctx. */
 size_t wdno_linattn_ws_bytes(int64_t units, int heads);
@@ -427,6 +459,13 @@ int wdno_linattn_fwd_amax(const float* qkv, float* out, float* kstats, float* ct
                           float scale, wdno_stream_t s);
 int wdno_linattn_bwd_amax(const float* qkv, const float* dout, const float* kstats, const float* ctx, float* dqkv, float* amax_rec,
                           void* ws, size_t ws_bytes, int64_t units, int n_tok, int heads, float scale, wdno_stream_t s);
+/* The cuts of a linear-attention call (nothing is launched; the launch paths ask the same code). backward = 0: kstats_chunks = pieces of the
+ * token range of the k statistics (n_tok / 64 within 1 .. 16; 0 for the backward, which reads kstats); ctx_chunks = pieces of the token range
+ * of the context (the backward: of dctx; 1 when units * heads exceeds 2 x CUs, else at most n_tok / 128 and 16); token_tiles = blocks along the
+ * tokens of the per-token kernel (128 tokens each; 64 for the thread-per-token family); family 0 = matrix kernels, 1 = thread per token
+ * (debug mode 5). rc: the code the launch would return, WDNO_EWORKSPACE for a backward with ws_bytes below wdno_linattn_ws_bytes. */
+typedef struct { int kstats_chunks, ctx_chunks, token_tiles, family, rc; } wdno_la_plan;
+int wdno_linattn_plan(int64_t units, int n_tok, int heads, int backward, size_t ws_bytes, wdno_la_plan* out);
 /* The same with dqkv delivered as fp16 (hi, lo) planes (see wdno_attn_bwd_planes); the scale bound uses the amax records of qkv and
  * dout and the measured max|dctx| (rec_dctx: a zeroed record the call fills). */
 int wdno_linattn_bwd_planes(const float* qkv, const float* dout, const float* kstats, const float* ctx, void* dqkv_hi, void* dqkv_lo,

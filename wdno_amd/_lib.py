@@ -47,6 +47,21 @@ class ConvPlan(C.Structure):                 # include/wdno_hip.h: wdno_conv_pla
     _fields_ = [(k, I) for k in ('family', 'bm', 'bn', 'uniform', 'tsplit', 'ksplit', 'ntiles', 'grid')]
 
 
+class AttnPlan(C.Structure):                 # include/wdno_hip.h: wdno_attn_plan
+    _fields_ = [(k, I) for k in ('family', 'grid', 'items_per_block', 'max_walk', 'dbias_partials', 'dbias_in_lds', 'lds_bytes', 'rc')]
+
+
+ATTN_FAMILIES = ('mfma24', 'mfma', 'mfma64', 'tiled', 'tiled_staged', 'tiled_unstaged', 'big', 'rows')      # WDNO_ATTN_*; -1: none
+
+
+class LinAttnPlan(C.Structure):              # include/wdno_hip.h: wdno_la_plan
+    _fields_ = [(k, I) for k in ('kstats_chunks', 'ctx_chunks', 'token_tiles', 'family', 'rc')]
+
+
+class LayerNormPlan(C.Structure):            # include/wdno_hip.h: wdno_ln_plan
+    _fields_ = [(k, I) for k in ('tpr', 'vpl', 'rows_per_block', 'blocks', 'max_rows_walk', 'rc')]
+
+
 class ConvWgradPlan(C.Structure):            # include/wdno_hip.h: wdno_wgrad_plan
     _fields_ = [(k, I) for k in ('family', 'bm', 'bn', 'splits', 'pix_per_split', 'splitpair', 'reduce_tiled', 'items', 'grid')]
 
@@ -198,6 +213,10 @@ PROTOTYPES = {
     'wdno_attn_fwd_planes': (I, [P, P, P, P, P, P, P, P, P, P, PA, F, P]),
     'wdno_linattn_fwd_planes': (I, [P, P, P, P, P, P, P, L, I, I, F, P]),
     'wdno_attn_bwd_planes': (I, [P, P, P, P, P, P, P, P, P, P, P, P, PA, F, P, Z, P]),
+    'wdno_attn_fwd_plan': (I, [PA, I, I, I, I, P]),
+    'wdno_attn_bwd_plan': (I, [PA, I, I, I, I, P]),
+    'wdno_linattn_plan': (I, [L, I, I, I, Z, P]),
+    'wdno_layernorm_plan': (I, [L, I, P]),
     'wdno_tattn_fused_takes': (I, [I, I, I]),
     'wdno_tattn_fused_fwd': (I, [P, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, L, I, I, F, P]),
     'wdno_lattn_fused_takes': (I, [I, I, I]),

@@ -26,6 +26,7 @@ struct AttnP {
   int ipb;  // items (unit, head) per block
   int kst;  // LDS floats per item for one [n][32] matrix (padded)
   int64_t n_items;
+  int db_slices;   // matrix backward, bias gradient in LDS: 1 = one [heads][n][n] partial per wave (heads % 4 != 0: two waves can hold the same head)
   float* amax_rec;   // optional amax record (common.h) of the tensor the kernel writes: out (forward), dqkv (backward)
   // backward with dqkv delivered as fp16 (hi, lo) planes (wdno_attn_bwd_planes): the plane pointers, the amax records of qkv and
   // dout the scale bound is derived from, and where the scale is left
@@ -1059,13 +1060,17 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
   float* St = Tb;
   float* dBs = smem + AM_WAVES * WAVE_LDS;            // [heads][n][n] when dbias
   // Relative-position-bias gradient = sum of dS over the units. With heads == AM_WAVES a wave always works on the head `wave`
-  // (item = 4 (block + k grid) + wave), so it sums its items' dS tiles in REGISTERS, in item order; otherwise LDS atomics.
+  // (item = 4 (block + k grid) + wave), so it sums its items' dS tiles in REGISTERS, in item order; otherwise in LDS. With heads a multiple
+  // of AM_WAVES the four waves of a block never hold the same head, so each (head, i, j) has ONE writer, which adds its items in order.
+  // With any other head count two waves can meet on a head, and the order of their additions would differ from run to run: there
+  // (p.db_slices) every wave owns a partial [heads][n][n] of its own and the block adds the four in wave order at the end.
   const bool db_regs = dbias && p.d.heads == AM_WAVES;
+  float* dBw = dBs + (p.db_slices ? (size_t)wave * p.d.heads * n * n : 0);
   f32x16 dbacc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) dbacc[e] = 0.f;
   if (dbias && !db_regs) {
-    for (int e = threadIdx.x; e < p.d.heads * n * n; e += 64 * AM_WAVES) dBs[e] = 0.f;
+    for (int e = threadIdx.x; e < (p.db_slices ? AM_WAVES : 1) * p.d.heads * n * n; e += 64 * AM_WAVES) dBs[e] = 0.f;
     __syncthreads();
   }
   const bool tok = li < n;
@@ -1183,7 +1188,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
       const int j = tf_key(e, hh);
       St[j * AM_TS + li] = dsT[e];
       if (db_regs) dbacc[e] += dsT[e];                 // entries with li >= n or j >= n are never written out
-      else if (dbias && tok && j < n) atomicAdd(&dBs[(h * n + li) * n + j], dsT[e]);
+      else if (dbias && tok && j < n) atomicAdd(&dBw[(h * n + li) * n + j], dsT[e]);      // (one writer per address: see above)
     }
     __builtin_amdgcn_wave_barrier();
     // dK^T[d][j] = sum_i Q[i][d] dS[i][j]: Q columns from the staged (scaled, rotated) tile
@@ -1274,19 +1279,20 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
       }
     } else {
       __syncthreads();
-      for (int e = threadIdx.x; e < p.d.heads * n * n; e += 64 * AM_WAVES) part[e] = dBs[e];
+      const int E = p.d.heads * n * n;
+      for (int e = threadIdx.x; e < E; e += 64 * AM_WAVES) part[e] = p.db_slices ? (dBs[e] + dBs[E + e]) + (dBs[2 * E + e] + dBs[3 * E + e]) : dBs[e];
     }
   }
 }
 
+#define ATT_MFMA64_LDS ((size_t)AM_WAVES * 2 * 64 * AM_TS * sizeof(float))       // 73.7 KB: two blocks per CU
+#define ATT_MFMA64_MAXBLOCKS 4096
+#define ATT_ROWS_MAXLDS (160 * 1024)
 static void attn_fwd_mfma64_launch(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
-                                   const AttnP& p, hipStream_t st) {
-  const size_t lds = (size_t)AM_WAVES * 2 * 64 * AM_TS * sizeof(float);       // 73.7 KB: two blocks per CU
+                                   const AttnP& p, int nb, hipStream_t st) {
   static bool done = false;
-  if (!done) { (void)hipFuncSetAttribute((const void*)attn_fwd_mfma64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
-  int64_t nb = (p.n_items + AM_WAVES - 1) / AM_WAVES;
-  if (nb > 4096) nb = 4096;
-  attn_fwd_mfma64_kernel<<<(unsigned)nb, 64 * AM_WAVES, lds, st>>>(qkv, rot_cos, rot_sin, bias, out, p);
+  if (!done) { (void)hipFuncSetAttribute((const void*)attn_fwd_mfma64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_MFMA64_LDS); done = true; }
+  attn_fwd_mfma64_kernel<<<(unsigned)nb, 64 * AM_WAVES, ATT_MFMA64_LDS, st>>>(qkv, rot_cos, rot_sin, bias, out, p);
 }
 // Grid of the one-wave-per-item kernels: exactly the blocks that are RESIDENT together (blocks per CU x CUs), each wave walking over
 // its items with a grid stride. The first versions launched up to 4096 / 2048 blocks: several rounds of the resident set with the last
@@ -1304,10 +1310,118 @@ static int attn_fill(AttnP& p, const wdno_attn_desc* d, float scale, int threads
   if (p.ipb < 1) p.ipb = 1;
   p.kst = d->n_tok * DH + 8;          // +8 floats: items start on different 32-byte LDS slots
   p.n_items = (int64_t)d->n_uo * d->n_ui * d->heads;
-  p.amax_rec = nullptr;
+  p.amax_rec = nullptr; p.db_slices = 0;
   p.pl_hi = p.pl_lo = nullptr; p.rec_qkv = p.rec_dout = nullptr; p.pl_scale = nullptr;
   return WDNO_OK;
 }
+
+// ---- what a call launches: the ONE place that decides it (the launch paths below and the plan queries of wdno_hip.h both ask here)
+static int attn_plan_refuse(wdno_attn_plan& pl, int rc) {
+  pl = wdno_attn_plan{WDNO_ATTN_NONE, 0, 0, 0, 0, 0, 0, rc};
+  return rc;
+}
+static void attn_plan_set(wdno_attn_plan& pl, int family, int64_t grid, int ipb, int64_t work, size_t lds) {
+  pl = wdno_attn_plan{family, (int)grid, ipb, (int)cdiv64(work, grid * ipb), 0, 0, (int)lds, WDNO_OK};
+}
+static int attn_mfma_family(int n) { return n == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? WDNO_ATTN_MFMA24 : WDNO_ATTN_MFMA; }
+static int attn_fwd_choose(const wdno_attn_desc* d, bool rot, bool bias, bool planes, wdno_attn_plan& pl) {
+  if (!d || d->n_uo <= 0 || d->n_ui <= 0 || d->n_tok <= 0 || d->heads <= 0) return attn_plan_refuse(pl, WDNO_EINVAL);
+  const int n = d->n_tok;
+  const int64_t items = (int64_t)d->n_uo * d->n_ui * d->heads;
+  const bool rows_mode = wdno_debug_mode == WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV;
+  if (planes ? n > 64 : n > 1024) return attn_plan_refuse(pl, WDNO_EUNSUPPORTED);
+  if (n <= 32 && (planes || !rows_mode)) {                       // one 32x32 MFMA tile per (unit, head): one wave per item
+    attn_plan_set(pl, attn_mfma_family(n), attn_grid(items, 4), AM_WAVES, items, 0);
+    return WDNO_OK;
+  }
+  if (n <= 64 && (planes || !rows_mode)) {                       // two 32-wide tiles of keys and of queries per item
+    int64_t nb = cdiv64(items, AM_WAVES);
+    if (nb > ATT_MFMA64_MAXBLOCKS) nb = ATT_MFMA64_MAXBLOCKS;
+    attn_plan_set(pl, WDNO_ATTN_MFMA64, nb, AM_WAVES, items, ATT_MFMA64_LDS);
+    return WDNO_OK;
+  }
+  if (!rot && !bias && !rows_mode && wdno_debug_mode != WDNO_DBG_ATTN_FWD_ROWS) {      // key tiles with an online softmax, one wave per tile of 32 queries (WDNO_DBG_ATTN_FWD_ROWS: thread per row)
+    const int64_t work = items * ((n + 31) / 32);
+    attn_plan_set(pl, WDNO_ATTN_TILED, attn_grid(work, 3), AM_WAVES, work, 0);
+    return WDNO_OK;
+  }
+  int ipb = ATT_THREADS / n;
+  if (ipb < 1) ipb = 1;
+  const size_t lds = (size_t)ipb * (n * DH + 8) * sizeof(float);
+  const int64_t blocks = cdiv64(items, ipb);
+  if (lds > ATT_ROWS_MAXLDS || blocks > 0x7fffffff) return attn_plan_refuse(pl, WDNO_EUNSUPPORTED);
+  attn_plan_set(pl, WDNO_ATTN_ROWS, blocks, ipb, items, lds);
+  return WDNO_OK;
+}
+// LDS floats of the thread-per-row backward: K, Q, P, dS per item slot and the block's bias-gradient partial
+static size_t attn_bwd_rows_lds(int n, int heads, int ipb, bool dbias) {
+  return ((size_t)ipb * (2 * (n * DH + 8) + 2 * n * (n + 1)) + (dbias ? (size_t)heads * n * n : 0)) * sizeof(float);
+}
+static int attn_bwd_choose(const wdno_attn_desc* d, bool rot, bool bias, bool dbias, bool planes, bool has_out, wdno_attn_plan& pl) {
+  if (!d || d->n_uo <= 0 || d->n_ui <= 0 || d->n_tok <= 0 || d->heads <= 0) return attn_plan_refuse(pl, WDNO_EINVAL);
+  const int n = d->n_tok;
+  const int64_t items = (int64_t)d->n_uo * d->n_ui * d->heads;
+  const bool rows_mode = wdno_debug_mode == WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV;
+  if (planes && (n > 32 || rows_mode)) return attn_plan_refuse(pl, WDNO_EUNSUPPORTED);
+  // one wave per item on MFMA tiles (WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV: thread-per-row kernel below); 116 registers and 9 KB of LDS per wave, so four
+  // waves per SIMD hide its five dependent load phases (0.94 vs 1.17 ms at the 40 x 40 level)
+  if (n <= 32 && !rows_mode) {
+    const bool in_lds = dbias && d->heads != AM_WAVES;            // (heads == AM_WAVES: the partial lives in registers)
+    const size_t base = (size_t)AM_WAVES * (2 * 32 * AM_TS + 32) * sizeof(float), one = (size_t)d->heads * n * n * sizeof(float);
+    // heads % AM_WAVES != 0: a partial per wave, so that no two waves add to one address (attn_bwd_mfma_kernel); one shared partial where four do not fit
+    // (from 9 heads on at 32 tokens: two waves of a block then add to one address in arrival order, reported as dbias_in_lds = 2)
+    const bool per_wave = in_lds && d->heads % AM_WAVES != 0 && base + AM_WAVES * one <= ATT_ROWS_MAXLDS;
+    const int arrays = !in_lds ? 0 : (per_wave ? AM_WAVES : 1);
+    if (base + arrays * one > ATT_ROWS_MAXLDS) return attn_plan_refuse(pl, WDNO_EUNSUPPORTED);
+    attn_plan_set(pl, attn_mfma_family(n), attn_grid(items, ATT_BWD_BLOCKS_PER_CU), AM_WAVES, items, base + arrays * one);
+    pl.dbias_partials = dbias ? pl.grid : 0;
+    pl.dbias_in_lds = !in_lds ? 0 : (per_wave ? AM_WAVES : (d->heads % AM_WAVES == 0 ? 1 : 2));
+    return WDNO_OK;
+  }
+  // more than 64 tokens without rotation / bias (the mid spatial block): key / query tiles on the exact-fp32 matrix instruction (WDNO_DBG_ATTN_BWD_ROWS: thread per row)
+  if (n > 64 && n <= ATT_TILED_MAXTOK && !rot && !bias && !dbias && has_out && !rows_mode && wdno_debug_mode != WDNO_DBG_ATTN_BWD_ROWS) {
+    const int64_t cap = 2LL * wdno_num_cus();
+    attn_plan_set(pl, n <= ATT_TILED_STAGE ? WDNO_ATTN_TILED_STAGED : WDNO_ATTN_TILED_UNSTAGED, items > cap ? cap : items, 1, items, 0);
+    return WDNO_OK;
+  }
+  // 129 .. 576 tokens: nothing n x n is stored (attn_bwd_big_kernel) -- and 64 .. 128 tokens too when the kernel takes the case (no rotation, no bias):
+  // the thread-per-row kernel keeps P and dS (2 n^2 floats: 81 KB at the mid block's 100 tokens) in LDS, one block per CU; 27 KB and five blocks per CU
+  // here: 305 -> 246 us for the mid spatial attention of the smoke U-Net
+  if (n > ATT_BWD_THREADS || (n >= 64 && !rot && !bias && !dbias)) {
+    if (n > ATT_BIG_MAXTOK || rot || bias || dbias) return attn_plan_refuse(pl, WDNO_EUNSUPPORTED);
+    const int64_t cap = 4LL * wdno_num_cus();
+    attn_plan_set(pl, WDNO_ATTN_BIG, items > cap ? cap : items, 1, items, ((size_t)2 * n * DH + 3 * n) * sizeof(float));
+    return WDNO_OK;
+  }
+  // thread per row: 128 / n items per block, fewer where their matrices and the bias-gradient partial do not fit the 160 KB of LDS together
+  // (64 tokens, 4 heads, a bias gradient: 164 992 bytes at two items, 115 264 at one)
+  int ipb = ATT_BWD_THREADS / n;
+  if (ipb < 1) ipb = 1;
+  if (dbias && ipb > d->heads) ipb = d->heads;             // the items of a block hold different heads: one writer per address of the partial, in item order
+  while (ipb > 1 && attn_bwd_rows_lds(n, d->heads, ipb, dbias) > ATT_ROWS_MAXLDS) --ipb;
+  const size_t lds = attn_bwd_rows_lds(n, d->heads, ipb, dbias);
+  if (lds > ATT_ROWS_MAXLDS) return attn_plan_refuse(pl, WDNO_EUNSUPPORTED);
+  const int64_t groups = cdiv64(items, ipb);
+  int64_t blocks = groups;
+  if (dbias && blocks > 1024) blocks = 1024;               // one dbias partial per block (grid-stride over the groups)
+  if (blocks > 0x7fffffff) return attn_plan_refuse(pl, WDNO_EUNSUPPORTED);
+  attn_plan_set(pl, WDNO_ATTN_ROWS, blocks, ipb, items, lds);
+  pl.dbias_partials = dbias ? pl.grid : 0;
+  pl.dbias_in_lds = dbias;
+  return WDNO_OK;
+}
+extern "C" int wdno_attn_fwd_plan(const wdno_attn_desc* d, int has_rot, int has_bias, int want_dbias, int planes, wdno_attn_plan* out) {
+  (void)want_dbias;
+  if (!out) return WDNO_EINVAL;
+  attn_fwd_choose(d, has_rot != 0, has_bias != 0, planes != 0, *out);
+  return WDNO_OK;
+}
+extern "C" int wdno_attn_bwd_plan(const wdno_attn_desc* d, int has_rot, int has_bias, int want_dbias, int planes, wdno_attn_plan* out) {
+  if (!out) return WDNO_EINVAL;
+  attn_bwd_choose(d, has_rot != 0, has_bias != 0, want_dbias != 0, planes != 0, true, *out);
+  return WDNO_OK;
+}
+
 extern "C" int wdno_attn_fwd(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
                              const wdno_attn_desc* d, float scale, wdno_stream_t s) {
   return wdno_attn_fwd_amax(qkv, rot_cos, rot_sin, bias, out, nullptr, d, scale, s);
@@ -1317,70 +1431,55 @@ static int attn_amax_sweep(int rc, const float* t, const wdno_attn_desc* d, int 
   if (rc != WDNO_OK || !amax_rec) return rc;
   return wdno_amax_record(t, (int64_t)d->n_uo * d->n_ui * d->n_tok * width, amax_rec, s);
 }
-static int attn_fwd_rows(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out, AttnP& p,
-                         const wdno_attn_desc* d, wdno_stream_t s);
+// the forward launch of a plan (p.amax_rec and the plane fields are the caller's)
+static int attn_fwd_launch(const wdno_attn_plan& pl, const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
+                           AttnP& p, wdno_stream_t s) {
+  switch (pl.family) {
+    case WDNO_ATTN_MFMA24: attn_fwd_mfma_kernel<24><<<(unsigned)pl.grid, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p); break;
+    case WDNO_ATTN_MFMA: attn_fwd_mfma_kernel<0><<<(unsigned)pl.grid, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p); break;
+    case WDNO_ATTN_MFMA64: attn_fwd_mfma64_launch(qkv, rot_cos, rot_sin, bias, out, p, pl.grid, as_stream(s)); break;
+    case WDNO_ATTN_TILED: attn_fwd_mfma_tiled_kernel<<<(unsigned)pl.grid, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, p); break;
+    case WDNO_ATTN_ROWS:
+      p.ipb = pl.items_per_block;
+      if (pl.lds_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+      attn_fwd_kernel<<<(unsigned)pl.grid, ATT_THREADS, (size_t)pl.lds_bytes, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
+      break;
+    default: return WDNO_EUNSUPPORTED;
+  }
+  return wdno_check_launch();
+}
 extern "C" int wdno_attn_fwd_amax(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
                                   float* amax_rec, const wdno_attn_desc* d, float scale, wdno_stream_t s) {
   AttnP p;
   int rc = attn_fill(p, d, scale, ATT_THREADS);
   if (rc) return rc;
-  if (d->n_tok > 1024) return WDNO_EUNSUPPORTED;
-  if (d->n_tok <= 32 && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {                  // one 32x32 MFMA tile per (unit, head): one wave per item
-    const int64_t nb = attn_grid(p.n_items, 4);
-    p.amax_rec = amax_rec;
-    (d->n_tok == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? attn_fwd_mfma_kernel<24> : attn_fwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
-    return wdno_check_launch();
-  }
-  if (d->n_tok <= 64 && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {                  // two 32-wide tiles of keys and of queries per item
-    p.amax_rec = amax_rec;
-    attn_fwd_mfma64_launch(qkv, rot_cos, rot_sin, bias, out, p, as_stream(s));
-    return wdno_check_launch();
-  }
-  if (!rot_cos && !bias && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV && wdno_debug_mode != WDNO_DBG_ATTN_FWD_ROWS) {      // key tiles with an online softmax, one wave per tile of 32 queries (WDNO_DBG_ATTN_FWD_ROWS: thread per row)
-    const int ntile = (d->n_tok + 31) / 32;
-    const int64_t nb = attn_grid(p.n_items * ntile, 3);
-    p.amax_rec = amax_rec;
-    attn_fwd_mfma_tiled_kernel<<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, p);
-    return wdno_check_launch();
-  }
-  return attn_amax_sweep(attn_fwd_rows(qkv, rot_cos, rot_sin, bias, out, p, d, s), out, d, p.HD, amax_rec, s);
+  wdno_attn_plan pl;
+  rc = attn_fwd_choose(d, rot_cos != nullptr, bias != nullptr, false, pl);
+  if (rc) return rc;
+  if (pl.family == WDNO_ATTN_ROWS) return attn_amax_sweep(attn_fwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, p, s), out, d, p.HD, amax_rec, s);
+  p.amax_rec = amax_rec;
+  return attn_fwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, p, s);
 }
-// forward with out delivered ONLY as fp16 planes for the to_out projection (MFMA path only: n_tok <= 32; `out` is not written)
+// forward with out delivered ONLY as fp16 planes for the to_out projection (MFMA paths only: n_tok <= 64; `out` is not written)
 extern "C" int wdno_attn_fwd_planes(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
                                     void* out_hi, void* out_lo, float* out_scale, float* amax_rec, const float* rec_qkv,
                                     const wdno_attn_desc* d, float scale, wdno_stream_t s) {
   AttnP p;
   int rc = attn_fill(p, d, scale, ATT_THREADS);
   if (rc) return rc;
-  if (d->n_tok > 64 || !out_hi || (out_lo && (!out_scale || !rec_qkv))) return WDNO_EUNSUPPORTED;      // out_lo == NULL: one bf16 plane
-  const int64_t nb = attn_grid(p.n_items, 4);
+  wdno_attn_plan pl;
+  rc = attn_fwd_choose(d, rot_cos != nullptr, bias != nullptr, true, pl);
+  if (rc) return rc;
+  if (!out_hi || (out_lo && (!out_scale || !rec_qkv))) return WDNO_EUNSUPPORTED;      // out_lo == NULL: one bf16 plane
   p.amax_rec = amax_rec;
   p.pl_hi = (_Float16*)out_hi; p.pl_lo = (_Float16*)out_lo; p.rec_qkv = rec_qkv; p.pl_scale = out_scale;
-  if (d->n_tok > 32) {
-    attn_fwd_mfma64_launch(qkv, rot_cos, rot_sin, bias, out, p, as_stream(s));
-    return wdno_check_launch();
-  }
-  (d->n_tok == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? attn_fwd_mfma_kernel<24> : attn_fwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
-  return wdno_check_launch();
+  return attn_fwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, p, s);
 }
-static int attn_fwd_rows(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out, AttnP& p,
-                         const wdno_attn_desc* d, wdno_stream_t s) {
-  size_t lds = (size_t)p.ipb * p.kst * sizeof(float);
-  if (lds > 160 * 1024) return WDNO_EUNSUPPORTED;
-  int64_t blocks = (p.n_items + p.ipb - 1) / p.ipb;
-  if (blocks > 0x7fffffff) return WDNO_EUNSUPPORTED;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  attn_fwd_kernel<<<(unsigned)blocks, ATT_THREADS, lds, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
-  return wdno_check_launch();
-}
-// blocks of the backward launch (= number of dbias partials) and the workspace that holds them
+// blocks of the backward launch with a bias gradient (= number of dbias partials) and the workspace that holds them; none for a shape the
+// backward refuses (the launch paths return that refusal before they look at the workspace)
 static int64_t attn_bwd_blocks(const wdno_attn_desc* d) {
-  const int64_t items = (int64_t)d->n_uo * d->n_ui * d->heads;
-  if (d->n_tok <= 32 && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) return attn_grid(items, ATT_BWD_BLOCKS_PER_CU);
-  int ipb = ATT_BWD_THREADS / d->n_tok;
-  if (ipb < 1) ipb = 1;
-  int64_t groups = (items + ipb - 1) / ipb;
-  return groups > 1024 ? 1024 : groups;
+  wdno_attn_plan pl;
+  return attn_bwd_choose(d, true, true, true, false, true, pl) ? 0 : pl.grid;
 }
 extern "C" size_t wdno_attn_bwd_ws_bytes(const wdno_attn_desc* d) {
   if (!d || d->n_tok <= 0 || d->heads <= 0) return 0;
@@ -1396,39 +1495,49 @@ extern "C" int wdno_attn_bwd(const float* qkv, const float* rot_cos, const float
                              wdno_stream_t s) {
   return wdno_attn_bwd_amax(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, dbias, nullptr, d, scale, ws, ws_bytes, s);
 }
-static int attn_bwd_rows(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out,
-                         const float* dout, float* dqkv, float* dbias, AttnP& p, const wdno_attn_desc* d, wdno_stream_t s);
+// the backward launch of a plan; part = the workspace of the dbias partials or NULL
+static int attn_bwd_launch(const wdno_attn_plan& pl, const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias,
+                           const float* out, const float* dout, float* dqkv, float* part, AttnP& p, wdno_stream_t s) {
+  const unsigned nb = (unsigned)pl.grid;
+  const size_t lds = (size_t)pl.lds_bytes;
+  p.db_slices = pl.dbias_in_lds == AM_WAVES;
+  if ((pl.family == WDNO_ATTN_MFMA24 || pl.family == WDNO_ATTN_MFMA) && pl.lds_bytes > 64 * 1024)
+    (void)hipFuncSetAttribute(pl.family == WDNO_ATTN_MFMA24 ? (const void*)attn_bwd_mfma_kernel<24> : (const void*)attn_bwd_mfma_kernel<0>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+  switch (pl.family) {
+    case WDNO_ATTN_MFMA24: attn_bwd_mfma_kernel<24><<<nb, 64 * AM_WAVES, lds, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p); break;
+    case WDNO_ATTN_MFMA: attn_bwd_mfma_kernel<0><<<nb, 64 * AM_WAVES, lds, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p); break;
+    case WDNO_ATTN_TILED_STAGED: attn_bwd_mfma_tiled_kernel<true><<<nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, dout, dqkv, p); break;
+    case WDNO_ATTN_TILED_UNSTAGED: attn_bwd_mfma_tiled_kernel<false><<<nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, dout, dqkv, p); break;
+    case WDNO_ATTN_BIG:
+      (void)hipFuncSetAttribute((const void*)attn_bwd_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+      attn_bwd_big_kernel<<<nb, ATT_BIG_THREADS, lds, as_stream(s)>>>(qkv, out, dout, dqkv, p);
+      break;
+    case WDNO_ATTN_ROWS:
+      p.ipb = pl.items_per_block;
+      if (pl.lds_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+      attn_bwd_kernel<<<nb, ATT_BWD_THREADS, lds, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p);
+      break;
+    default: return WDNO_EUNSUPPORTED;
+  }
+  return wdno_check_launch();
+}
 extern "C" int wdno_attn_bwd_amax(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out,
                                   const float* dout, float* dqkv, float* dbias, float* amax_rec, const wdno_attn_desc* d, float scale,
                                   void* ws, size_t ws_bytes, wdno_stream_t s) {
   AttnP p;
   int rc = attn_fill(p, d, scale, ATT_BWD_THREADS);
   if (rc) return rc;
-  const int n = d->n_tok;
+  wdno_attn_plan pl;
+  rc = attn_bwd_choose(d, rot_cos != nullptr, bias != nullptr, dbias != nullptr, false, out != nullptr, pl);
+  if (rc) return rc;
   if (dbias && (!ws || ws_bytes < wdno_attn_bwd_ws_bytes(d))) return WDNO_EWORKSPACE;
   float* part = dbias ? (float*)ws : nullptr;           // the kernels write per-block partials; the reduce below writes dbias
-  // one wave per item on MFMA tiles (WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV: thread-per-row kernel below); 116 registers and 9 KB of LDS per wave, so four
-  // waves per SIMD hide its five dependent load phases (0.94 vs 1.17 ms at the 40 x 40 level)
-  if (n <= 32 && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {
-    size_t lds2 = ((size_t)AM_WAVES * (2 * 32 * AM_TS + 32) + (dbias && d->heads != AM_WAVES ? (size_t)d->heads * n * n : 0)) * sizeof(float);      // (heads == AM_WAVES: the partial lives in registers)
-    const int64_t nb = attn_bwd_blocks(d);                   // also the number of dbias partials
-    p.amax_rec = amax_rec;
-    (d->n_tok == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? attn_bwd_mfma_kernel<24> : attn_bwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, lds2, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p);
-    rc = wdno_check_launch();
-    return (rc || !dbias) ? rc : attn_dbias_reduce(part, nb, dbias, d, s);
-  }
-  // more than 64 tokens without rotation / bias (the mid spatial block): key / query tiles on the exact-fp32 matrix instruction (WDNO_DBG_ATTN_BWD_ROWS: thread per row)
-  if (n > 64 && n <= ATT_TILED_MAXTOK && !rot_cos && !bias && !dbias && out && wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV && wdno_debug_mode != WDNO_DBG_ATTN_BWD_ROWS) {
-    int64_t nb = p.n_items;
-    const int64_t cap = 2LL * wdno_num_cus();
-    if (nb > cap) nb = cap;
-    p.amax_rec = amax_rec;
-    if (n <= ATT_TILED_STAGE) attn_bwd_mfma_tiled_kernel<true><<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, dout, dqkv, p);
-    else attn_bwd_mfma_tiled_kernel<false><<<(unsigned)nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, dout, dqkv, p);
-    return wdno_check_launch();
-  }
-  rc = attn_amax_sweep(attn_bwd_rows(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p, d, s), dqkv, d, p.RW, amax_rec, s);
-  return (rc || !dbias) ? rc : attn_dbias_reduce(part, attn_bwd_blocks(d), dbias, d, s);
+  const bool sweep = pl.family == WDNO_ATTN_BIG || pl.family == WDNO_ATTN_ROWS;      // these two do not track the amax of what they write
+  if (!sweep) p.amax_rec = amax_rec;
+  rc = attn_bwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p, s);
+  if (sweep) rc = attn_amax_sweep(rc, dqkv, d, p.RW, amax_rec, s);
+  return (rc || !dbias) ? rc : attn_dbias_reduce(part, pl.dbias_partials, dbias, d, s);
 }
 // dqkv as fp16 planes for the qkv projection's gradient kernels (MFMA path only: n_tok <= 32)
 extern "C" int wdno_attn_bwd_planes(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out,
@@ -1438,41 +1547,15 @@ extern "C" int wdno_attn_bwd_planes(const float* qkv, const float* rot_cos, cons
   AttnP p;
   int rc = attn_fill(p, d, scale, ATT_BWD_THREADS);
   if (rc) return rc;
-  const int n = d->n_tok;
-  if (n > 32 || wdno_debug_mode == WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV || !dqkv_hi || (dqkv_lo && (!dqkv_scale || !rec_qkv || !rec_dout))) return WDNO_EUNSUPPORTED;      // dqkv_lo == NULL: one bf16 plane, no scale
+  wdno_attn_plan pl;
+  rc = attn_bwd_choose(d, rot_cos != nullptr, bias != nullptr, dbias != nullptr, true, out != nullptr, pl);
+  if (rc) return rc;
+  if (!dqkv_hi || (dqkv_lo && (!dqkv_scale || !rec_qkv || !rec_dout))) return WDNO_EUNSUPPORTED;      // dqkv_lo == NULL: one bf16 plane, no scale
   if (dbias && (!ws || ws_bytes < wdno_attn_bwd_ws_bytes(d))) return WDNO_EWORKSPACE;
   float* part = dbias ? (float*)ws : nullptr;
-  size_t lds2 = ((size_t)AM_WAVES * (2 * 32 * AM_TS + 32) + (dbias && d->heads != AM_WAVES ? (size_t)d->heads * n * n : 0)) * sizeof(float);      // (heads == AM_WAVES: the partial lives in registers)
-  const int64_t nb = attn_bwd_blocks(d);
   p.pl_hi = (_Float16*)dqkv_hi; p.pl_lo = (_Float16*)dqkv_lo; p.rec_qkv = rec_qkv; p.rec_dout = rec_dout; p.pl_scale = dqkv_scale;
-  (d->n_tok == 24 && wdno_debug_mode != WDNO_DBG_ATTN_GENERIC_NTOK ? attn_bwd_mfma_kernel<24> : attn_bwd_mfma_kernel<0>)<<<(unsigned)nb, 64 * AM_WAVES, lds2, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, nullptr, part, p);
-  rc = wdno_check_launch();
-  return (rc || !dbias) ? rc : attn_dbias_reduce(part, nb, dbias, d, s);
-}
-static int attn_bwd_rows(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out,
-                         const float* dout, float* dqkv, float* dbias, AttnP& p, const wdno_attn_desc* d, wdno_stream_t s) {
-  const int n = d->n_tok;
-  // 129 .. 576 tokens: nothing n x n is stored (attn_bwd_big_kernel) -- and 64 .. 128 tokens too when the kernel takes the case (no rotation, no bias):
-  // the thread-per-row kernel keeps P and dS (2 n^2 floats: 81 KB at the mid block's 100 tokens) in LDS, one block per CU; 27 KB and five blocks per CU
-  // here: 305 -> 246 us for the mid spatial attention of the smoke U-Net
-  if (n > ATT_BWD_THREADS || (n >= 64 && !rot_cos && !bias && !dbias)) {
-    if (n > ATT_BIG_MAXTOK || rot_cos || bias || dbias) return WDNO_EUNSUPPORTED;
-    const size_t lds = ((size_t)2 * n * DH + 3 * n) * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int64_t nb = p.n_items;
-    const int64_t cap = 4LL * wdno_num_cus();
-    if (nb > cap) nb = cap;
-    attn_bwd_big_kernel<<<(unsigned)nb, ATT_BIG_THREADS, lds, as_stream(s)>>>(qkv, out, dout, dqkv, p);
-    return wdno_check_launch();
-  }
-  size_t lds = ((size_t)p.ipb * (2 * p.kst + 2 * n * (n + 1)) + (dbias ? (size_t)d->heads * n * n : 0)) * sizeof(float);
-  if (lds > 160 * 1024) return WDNO_EUNSUPPORTED;
-  int64_t groups = (p.n_items + p.ipb - 1) / p.ipb;
-  int64_t blocks = groups;
-  if (dbias && blocks > 1024) blocks = 1024;               // = attn_bwd_blocks(d): one dbias partial per block (grid-stride over the groups)
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  attn_bwd_kernel<<<(unsigned)blocks, ATT_BWD_THREADS, lds, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, dbias, p);
-  return wdno_check_launch();
+  rc = attn_bwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, dout, nullptr, part, p, s);
+  return (rc || !dbias) ? rc : attn_dbias_reduce(part, pl.dbias_partials, dbias, d, s);
 }
 
 // ================================================================================================ linear attention
@@ -1655,8 +1738,8 @@ static int la_ctx_chunks(int64_t units, int heads, int n_tok) {
 }
 template <int MODE>
 static void la_ctx_launch(const float* qkv, const float* other, const float* kstats, const float* ctx_in, float* ctx_out, float* tvec, float* part,
-                          int64_t units, int n_tok, int heads, float scale, hipStream_t st) {
-  const int chunks = part ? la_ctx_chunks(units, heads, n_tok) : 1;
+                          int64_t units, int n_tok, int heads, float scale, int chunks, hipStream_t st) {
+  if (!part) chunks = 1;
   linattn_ctx_kernel<MODE><<<(unsigned)(units * heads * chunks), 256, 0, st>>>(qkv, other, kstats, ctx_in, ctx_out, tvec, n_tok, heads, scale, chunks, part);
   if (chunks > 1) linattn_ctx_merge_kernel<MODE><<<(unsigned)(units * heads), 256, 0, st>>>(part, ctx_in, ctx_out, tvec, chunks);
 }
@@ -1929,7 +2012,7 @@ __global__ __launch_bounds__(256, 2) void linattn_bwd_tok_mfma_kernel(const floa
                                      scale * qsm[4 * e4 + 2] * (acc[4 * e4 + 2] - dot), scale * qsm[4 * e4 + 3] * (acc[4 * e4 + 3] - dot));
         vv[e4] = v;
         if (tok && !pl_hi) *reinterpret_cast<float4*>(db + 8 * e4 + 4 * hh) = v;
-        am = amax4(am, v);
+        if (tok) am = amax4(am, v);                      // lanes past the last token hold values of no token
       }
       if (tok && pl_hi) am_store_row_planes(pl_hi, pl_lo, pbase, hh, vv, ps);
     }
@@ -1953,7 +2036,7 @@ __global__ __launch_bounds__(256, 2) void linattn_bwd_tok_mfma_kernel(const floa
                                      expf(kk.z - m4.z) * l4.z * (acc[4 * e4 + 2] - t4.z), expf(kk.w - m4.w) * l4.w * (acc[4 * e4 + 3] - t4.w));
         vk[e4] = v;
         if (tok && !pl_hi) *reinterpret_cast<float4*>(db + HD + d0) = v;
-        am = amax4(am, v);
+        if (tok) am = amax4(am, v);
       }
       if (tok && pl_hi) am_store_row_planes(pl_hi, pl_lo, pbase + HD, hh, vk, ps);
     }
@@ -1976,7 +2059,7 @@ __global__ __launch_bounds__(256, 2) void linattn_bwd_tok_mfma_kernel(const floa
         const float4 v = make_float4(acc[4 * e4], acc[4 * e4 + 1], acc[4 * e4 + 2], acc[4 * e4 + 3]);
         vd[e4] = v;
         if (tok && !pl_hi) *reinterpret_cast<float4*>(db + 2 * HD + 8 * e4 + 4 * hh) = v;
-        am = amax4(am, v);
+        if (tok) am = amax4(am, v);
       }
       if (tok && pl_hi) am_store_row_planes(pl_hi, pl_lo, pbase + 2 * HD, hh, vd, ps);
     }
@@ -2063,18 +2146,38 @@ extern "C" size_t wdno_linattn_ws_bytes(int64_t units, int heads) {
   const size_t chunk_part = units * heads <= 2 * (int64_t)wdno_num_cus() ? (size_t)units * heads * LA_MAXCHUNKS * DH * DH : 0;      // partial contexts of a chunked token range
   return ((size_t)units * heads * DH * DH + (size_t)units * heads * DH + chunk_part) * sizeof(float);
 }
+// the cuts of a call: the ONE place that decides them (the launch paths below and wdno_linattn_plan both ask here)
+static int la_choose(int64_t units, int n_tok, int heads, bool backward, size_t ws_bytes, wdno_la_plan& pl) {
+  pl = wdno_la_plan{0, 0, 0, 0, la_check(units, n_tok, heads)};
+  if (pl.rc) return pl.rc;
+  if (backward && ws_bytes < wdno_linattn_ws_bytes(units, heads)) return pl.rc = WDNO_EWORKSPACE;
+  if (!backward) {
+    pl.kstats_chunks = n_tok / 64;
+    pl.kstats_chunks = pl.kstats_chunks < 1 ? 1 : (pl.kstats_chunks > 16 ? 16 : pl.kstats_chunks);
+  }
+  // forward: the chunk partials always have room (they go through `out` / the hi plane); backward: the workspace has the room only up to 2 x CUs (unit, head) pairs
+  pl.ctx_chunks = !backward || units * heads <= 2 * (int64_t)wdno_num_cus() ? la_ctx_chunks(units, heads, n_tok) : 1;
+  pl.family = wdno_debug_mode == WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV ? 1 : 0;
+  pl.token_tiles = cdiv(n_tok, pl.family ? 64 : 128);
+  return WDNO_OK;
+}
+extern "C" int wdno_linattn_plan(int64_t units, int n_tok, int heads, int backward, size_t ws_bytes, wdno_la_plan* out) {
+  if (!out) return WDNO_EINVAL;
+  la_choose(units, n_tok, heads, backward != 0, ws_bytes, *out);
+  return WDNO_OK;
+}
 extern "C" int wdno_linattn_fwd(const float* qkv, float* out, float* kstats, float* ctx, int64_t units, int n_tok, int heads,
                                 float scale, wdno_stream_t s) {
   return wdno_linattn_fwd_amax(qkv, out, kstats, ctx, nullptr, units, n_tok, heads, scale, s);
 }
 extern "C" int wdno_linattn_fwd_amax(const float* qkv, float* out, float* kstats, float* ctx, float* amax_rec, int64_t units, int n_tok,
                                      int heads, float scale, wdno_stream_t s) {
-  int rc = la_check(units, n_tok, heads);
+  wdno_la_plan pl;
+  int rc = la_choose(units, n_tok, heads, false, 0, pl);
   if (rc) return rc;
   hipStream_t st = as_stream(s);
   // partial statistics go through `ctx` (written only afterwards by the context kernel): chunks * HD * 2 <= 32 * HD floats per unit
-  int chunks = n_tok / 64;
-  chunks = chunks < 1 ? 1 : (chunks > 16 ? 16 : chunks);
+  const int chunks = pl.kstats_chunks;
   if (chunks == 1) {
     linattn_kstats_kernel<<<(unsigned)units, 256, 0, st>>>(qkv, kstats, n_tok, heads * DH, 1);
   } else {
@@ -2084,13 +2187,13 @@ extern "C" int wdno_linattn_fwd_amax(const float* qkv, float* out, float* kstats
   }
   // (chunk partials of the context go through `out`, which only the output kernel below writes: units * heads * chunks * 1024 floats
   // <= units * n_tok * HD because chunks <= n_tok / 128)
-  la_ctx_launch<0>(qkv, nullptr, kstats, nullptr, ctx, nullptr, out, units, n_tok, heads, scale, st);
-  if (wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {            // else: the thread-per-token kernel
-    linattn_out_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)cdiv(n_tok, 128)), 256, 0, st>>>(qkv, ctx, out, n_tok, heads, scale, amax_rec);
+  la_ctx_launch<0>(qkv, nullptr, kstats, nullptr, ctx, nullptr, out, units, n_tok, heads, scale, pl.ctx_chunks, st);
+  if (pl.family == 0) {            // else: the thread-per-token kernel
+    linattn_out_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)pl.token_tiles), 256, 0, st>>>(qkv, ctx, out, n_tok, heads, scale, amax_rec);
     return wdno_check_launch();
   }
   size_t lds = (size_t)heads * DH * DH * sizeof(float);
-  linattn_out_kernel<<<dim3((unsigned)units, (unsigned)cdiv(n_tok, 64)), 64 * heads, lds, st>>>(qkv, ctx, out, n_tok, heads, scale, amax_rec);
+  linattn_out_kernel<<<dim3((unsigned)units, (unsigned)pl.token_tiles), 64 * heads, lds, st>>>(qkv, ctx, out, n_tok, heads, scale, amax_rec);
   return wdno_check_launch();
 }
 extern "C" int wdno_linattn_bwd(const float* qkv, const float* dout, const float* kstats, const float* ctx, float* dqkv,
@@ -2100,25 +2203,25 @@ extern "C" int wdno_linattn_bwd(const float* qkv, const float* dout, const float
 extern "C" int wdno_linattn_bwd_amax(const float* qkv, const float* dout, const float* kstats, const float* ctx, float* dqkv,
                                      float* amax_rec, void* ws, size_t ws_bytes, int64_t units, int n_tok, int heads, float scale,
                                      wdno_stream_t s) {
-  int rc = la_check(units, n_tok, heads);
+  wdno_la_plan pl;
+  int rc = la_choose(units, n_tok, heads, true, ws_bytes, pl);
   if (rc) return rc;
-  if (ws_bytes < wdno_linattn_ws_bytes(units, heads)) return WDNO_EWORKSPACE;
   hipStream_t st = as_stream(s);
   float* dctx = (float*)ws;
   float* tvec = dctx + (size_t)units * heads * DH * DH;
-  float* cpart = ws_bytes >= wdno_linattn_ws_bytes(units, heads) && units * heads <= 2 * (int64_t)wdno_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
-  la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, st);
-  if (wdno_debug_mode != WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV) {            // else: the thread-per-token kernel
+  float* cpart = units * heads <= 2 * (int64_t)wdno_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
+  la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, pl.ctx_chunks, st);
+  if (pl.family == 0) {            // else: the thread-per-token kernel
     const size_t lds2 = ((size_t)(2 + 4 * 3) * LAM_TILE + 3 * DH) * sizeof(float);
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute((const void*)linattn_bwd_tok_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); attr_done = true; }
-    linattn_bwd_tok_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)cdiv(n_tok, 128)), 256, lds2, st>>>(qkv, dout, kstats, ctx, dctx, tvec,
+    linattn_bwd_tok_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)pl.token_tiles), 256, lds2, st>>>(qkv, dout, kstats, ctx, dctx, tvec,
                                                                                                           dqkv, n_tok, heads, scale, amax_rec);
     return wdno_check_launch();
   }
   size_t lds = ((size_t)2 * heads * DH * DH + 3 * heads * DH) * sizeof(float);
   if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)linattn_bwd_tok_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  linattn_bwd_tok_kernel<<<dim3((unsigned)units, (unsigned)cdiv(n_tok, 64)), 64 * heads, lds, st>>>(qkv, dout, kstats, ctx, dctx, tvec, dqkv,
+  linattn_bwd_tok_kernel<<<dim3((unsigned)units, (unsigned)pl.token_tiles), 64 * heads, lds, st>>>(qkv, dout, kstats, ctx, dctx, tvec, dqkv,
                                                                                                 n_tok, heads, scale, amax_rec);
   return wdno_check_launch();
 }
@@ -2131,12 +2234,14 @@ extern "C" int wdno_linattn_bwd_planes(const float* qkv, const float* dout, cons
   int rc = la_check(units, n_tok, heads);
   if (rc) return rc;
   if (!dqkv_hi || (dqkv_lo && (!dqkv_scale || !rec_qkv || !rec_dout || !rec_dctx))) return WDNO_EINVAL;      // dqkv_lo == NULL: one bf16 plane
-  if (ws_bytes < wdno_linattn_ws_bytes(units, heads)) return WDNO_EWORKSPACE;
+  wdno_la_plan pl;
+  rc = la_choose(units, n_tok, heads, true, ws_bytes, pl);
+  if (rc) return rc;
   hipStream_t st = as_stream(s);
   float* dctx = (float*)ws;
   float* tvec = dctx + (size_t)units * heads * DH * DH;
-  float* cpart = ws_bytes >= wdno_linattn_ws_bytes(units, heads) && units * heads <= 2 * (int64_t)wdno_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
-  la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, st);
+  float* cpart = units * heads <= 2 * (int64_t)wdno_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
+  la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, pl.ctx_chunks, st);
   if (dqkv_lo) {
     rc = wdno_amax_record(dctx, (int64_t)units * heads * DH * DH, rec_dctx, s);
     if (rc) return rc;
@@ -2156,9 +2261,10 @@ extern "C" int wdno_linattn_fwd_planes(const float* qkv, void* out_hi, void* out
   int rc = la_check(units, n_tok, heads);
   if (rc) return rc;
   if (!out_hi || (out_lo && (!out_scale || !rec_qkv))) return WDNO_EINVAL;      // out_lo == NULL: one bf16 plane
+  wdno_la_plan pl;
+  la_choose(units, n_tok, heads, false, 0, pl);
   hipStream_t st = as_stream(s);
-  int chunks = n_tok / 64;
-  chunks = chunks < 1 ? 1 : (chunks > 16 ? 16 : chunks);
+  const int chunks = pl.kstats_chunks;
   if (chunks == 1) {
     linattn_kstats_kernel<<<(unsigned)units, 256, 0, st>>>(qkv, kstats, n_tok, heads * DH, 1);
   } else {
@@ -2167,7 +2273,7 @@ extern "C" int wdno_linattn_fwd_planes(const float* qkv, void* out_hi, void* out
     linattn_kstats_merge_kernel<<<(unsigned)cdiv64(cols, 256), 256, 0, st>>>(ctx, kstats, cols, heads * DH, chunks);
   }
   // (chunk partials go through the hi plane: units * heads * chunks * 4096 bytes <= units * n_tok * HD * 2 because chunks <= n_tok / 128)
-  la_ctx_launch<0>(qkv, nullptr, kstats, nullptr, ctx, nullptr, (float*)out_hi, units, n_tok, heads, scale, st);
+  la_ctx_launch<0>(qkv, nullptr, kstats, nullptr, ctx, nullptr, (float*)out_hi, units, n_tok, heads, scale, pl.ctx_chunks, st);
   linattn_out_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)cdiv(n_tok, 128)), 256, 0, st>>>(
       qkv, ctx, nullptr, n_tok, heads, scale, nullptr, (_Float16*)out_hi, (_Float16*)out_lo, rec_qkv, out_scale);
   return wdno_check_launch();

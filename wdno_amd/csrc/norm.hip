@@ -951,13 +951,30 @@ static inline void ln_shape(int C, int& tpr, int& vpl) {
   if (c4 <= 64) { tpr = pow2ceil(c4); if (tpr < 2) tpr = 2; vpl = 1; }
   else { tpr = 64; vpl = pow2ceil(cdiv(c4, 64)); }
 }
+// the launch shape of P rows of C channels: the ONE place that decides it (ln_launch, the backward's partial count and wdno_layernorm_plan ask here)
+static int ln_choose(int64_t P, int C, wdno_ln_plan& pl) {
+  pl = wdno_ln_plan{0, 0, 0, 0, 0, WDNO_OK};
+  if (!(P > 0 && C >= 4)) return pl.rc = WDNO_EINVAL;
+  if ((C & 3) || C > 1024) return pl.rc = WDNO_EUNSUPPORTED;
+  ln_shape(C, pl.tpr, pl.vpl);
+  pl.rows_per_block = 256 / pl.tpr;
+  pl.blocks = ln_blocks(P, pl.rows_per_block);
+  pl.max_rows_walk = (int)cdiv64(P, (int64_t)pl.blocks * pl.rows_per_block);
+  return WDNO_OK;
+}
+extern "C" int wdno_layernorm_plan(int64_t P, int C, wdno_ln_plan* out) {
+  if (!out) return WDNO_EINVAL;
+  ln_choose(P, C, *out);
+  return WDNO_OK;
+}
 template <bool BWD>
 static int ln_launch(const float* x, const float* g, const float* dy, float* out, float* dgp, int64_t P, int C, float eps, hipStream_t st,
                      const float* add_to = nullptr, float* dx_amax = nullptr, _Float16* y_hi = nullptr, _Float16* y_lo = nullptr,
                      float* y_scale = nullptr) {
-  int tpr, vpl;
-  ln_shape(C, tpr, vpl);
-  int nb = ln_blocks(P, 256 / tpr);
+  wdno_ln_plan pl;
+  int rc = ln_choose(P, C, pl);
+  if (rc) return rc;
+  const int tpr = pl.tpr, vpl = pl.vpl, nb = pl.blocks;
 #define LN_CASE(T, V) layernorm_kernel<T, V, BWD><<<nb, 256, 0, st>>>(x, g, dy, out, dgp, P, C, eps, add_to, dx_amax, y_hi, y_lo, y_scale)
   if (vpl == 1) {
     switch (tpr) {
@@ -999,9 +1016,9 @@ extern "C" int wdno_layernorm_bwd_add_amax(const float* x, const float* g, const
   WDNO_REQUIRE(P > 0 && C >= 4);
   if ((C & 3) || C > 1024) return WDNO_EUNSUPPORTED;
   if (ws_bytes < wdno_layernorm_bwd_ws_bytes(P, C)) return WDNO_EWORKSPACE;
-  int tpr, vpl;
-  ln_shape(C, tpr, vpl);
-  int nb = ln_blocks(P, 256 / tpr);
+  wdno_ln_plan pl;
+  ln_choose(P, C, pl);
+  const int nb = pl.blocks;
   int rc = ln_launch<true>(x, g, dy, dx, (float*)ws, P, C, eps, as_stream(s), add_to, amax_rec);
   if (rc) return rc;
   partial_rows_sum_kernel<float><<<cdiv(C, 32), PRS_THREADS, 0, as_stream(s)>>>((const float*)ws, dg, nb, C);

@@ -2245,6 +2245,42 @@ def lattn_fused_plan(units, n_tok):
     return out
 
 
+def _plan_dict(pl):
+    return {k: getattr(pl, k) for k, _ in pl._fields_}
+
+
+def attn_plan(direction, heads, n_uo, n_ui, n_tok, so=0, si=0, st=1, rot=False, bias=False, dbias=False, planes=False):
+    """What softmax_attention launches forward (direction 'fwd') or backward ('bwd') for a unit / token layout, as the library's launch path
+    decides it under the current debug mode: the fields of _lib.AttnPlan as a dict, `family` as a name of _lib.ATTN_FAMILIES (None when the
+    call would be refused; `rc` is the code it would return). No launch, no device needed."""
+    pl = _lib.AttnPlan()
+    d = AttnDesc(n_uo, n_ui, n_tok, heads, so, si, st)
+    fn = {'fwd': _lib_().wdno_attn_fwd_plan, 'bwd': _lib_().wdno_attn_bwd_plan}[direction]
+    _lib.check(fn(C.byref(d), int(bool(rot)), int(bool(bias)), int(bool(dbias)), int(bool(planes)), C.byref(pl)), 'attn_plan')
+    out = _plan_dict(pl)
+    out['family'] = _lib.ATTN_FAMILIES[pl.family] if pl.family >= 0 else None
+    return out
+
+
+def linattn_plan(units, n_tok, heads, backward=False, ws_bytes=None):
+    """The cuts linear_attention makes (csrc/attention.hip): dict(kstats_chunks, ctx_chunks, token_tiles, family 'mfma' | 'tokens', rc).
+    ws_bytes None: the workspace the backward asks for. No launch, no device needed."""
+    pl = _lib.LinAttnPlan()
+    if ws_bytes is None:
+        ws_bytes = _lib_().wdno_linattn_ws_bytes(int(units), int(heads))
+    _lib.check(_lib_().wdno_linattn_plan(int(units), int(n_tok), int(heads), int(bool(backward)), int(ws_bytes), C.byref(pl)), 'linattn_plan')
+    out = _plan_dict(pl)
+    out['family'] = ('mfma', 'tokens')[pl.family]
+    return out
+
+
+def layernorm_plan(p, c):
+    """The launch shape of layernorm_cl for p rows of c channels: dict(tpr, vpl, rows_per_block, blocks, max_rows_walk, rc)."""
+    pl = _lib.LayerNormPlan()
+    _lib.check(_lib_().wdno_layernorm_plan(int(p), int(c), C.byref(pl)), 'layernorm_plan')
+    return _plan_dict(pl)
+
+
 class _RelPosBias(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, bucket):
