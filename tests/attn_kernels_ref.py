@@ -1,4 +1,4 @@
-"""The layer-by-layer attention kernels (csrc/attention.hip) and the channel LayerNorm (csrc/norm.hip) in plain torch on the CPU, fp64, forward
+"""The layer-by-layer attention kernels (csrc/attention.hip, csrc/linattn.hip) and the channel LayerNorm (csrc/norm.hip) in plain torch on the CPU, fp64, forward
 and hand-written backward (no autograd), with an ERROR SCALE per output, built stage by stage as tests/attn_ref.py's docstring describes. Test
 infrastructure only. Unlike attn_ref these start from a GIVEN qkv / x (exact fp32 inputs): no LayerNorm or projection in front, so a stage's
 scale starts from the rounding of its own terms:
@@ -448,7 +448,7 @@ def reference_of_l(name, cuts=(1, 1, 1)):
 
 
 def _merge32(m, l, m2, l2):
-    """softmax_merge of csrc/attention.hip"""
+    """softmax_merge of csrc/linattn.hip"""
     mn = torch.maximum(m, m2)
     a = torch.where(torch.isinf(m), torch.zeros_like(l), l * torch.exp(m - mn))
     b = torch.where(torch.isinf(m2), torch.zeros_like(l2), l2 * torch.exp(m2 - mn))
@@ -456,7 +456,7 @@ def _merge32(m, l, m2, l2):
 
 
 def _kstats32(k, heads, chunks):
-    """linattn_kstats_kernel + linattn_kstats_merge_kernel on k [U, h, n, 32]: (max, sum) [U, h, 32] each. A chunk's rows go round-robin to
+    """linattn_kstats_kernel + linattn_kstats_merge_kernel (csrc/linattn.hip) on k [U, h, n, 32]: (max, sum) [U, h, 32] each. A chunk's rows go round-robin to
     256 / HD row groups, each takes eight rows per round with one rescale per round; groups, then chunks, merge in order."""
     n = k.shape[2]
     nrg = 256 // (heads * DH)
@@ -483,7 +483,7 @@ def _kstats32(k, heads, chunks):
 
 
 def _chunk_sum32(a, b, chunks):
-    """sum_n a[n][d] b[n][e] as linattn_ctx_kernel cuts it: pieces of ((n / chunks rounded up) rounded up to 8) tokens, added in chunk order"""
+    """sum_n a[n][d] b[n][e] as linattn_ctx_kernel (csrc/linattn.hip) cuts it: pieces of ((n / chunks rounded up) rounded up to 8) tokens, added in chunk order"""
     n = a.shape[2]
     clen = (-(-n // chunks) + 7) & ~7
     tot = None
@@ -636,7 +636,7 @@ def transcription_ln(x, g, dy=None, add=None, rows_per_block=1, blocks=1):
 
 # ------------------------------------------------------------------------------------------------------------------ the plane-delivering forms
 # A tensor delivered as planes is (hi, lo) = (fp16(t s), fp16(t s - hi)) at ONE power-of-two scale s = scale_from_amax(bound), the bound an
-# analytic one of max|t| that the kernel forms in fp32 from the amax records of its inputs (csrc/attention.hip states each next to the code):
+# analytic one of max|t| that the kernel forms in fp32 from the amax records of its inputs (csrc/attention.hip and csrc/linattn.hip state each next to the code):
 #   softmax attention forward    |out|  <= A                                        (rows of P sum to 1; A = max|qkv|)
 #   softmax attention backward   |dqkv| <= 1.01 max(n G, 1.4143 scale n 64 G A^2)   (G = max|dout|)
 #   linear attention forward     |out|  <= 1.01 scale A

@@ -1,4 +1,4 @@
-"""The layer-by-layer attention kernels (csrc/attention.hip) and the channel LayerNorm (csrc/norm.hip) held ELEMENT BY ELEMENT to the fp64
+"""The layer-by-layer attention kernels (csrc/attention.hip, csrc/linattn.hip) and the channel LayerNorm (csrc/norm.hip) held ELEMENT BY ELEMENT to the fp64
 references of tests/attn_kernels_ref.py, |got - ref| <= K 2^-24 scale + flush, on a case matrix that visits every launch regime the plan queries
 (ops.attn_plan, ops.linattn_plan, ops.layernorm_plan) can report: every kernel family, one item up to a grid-stride walk with a second pass, the
 bias-gradient partial in registers and in LDS, every chunk count edge of the linear attention, every (lanes per row, vectors per lane) pair of the
@@ -286,8 +286,9 @@ def test_attention_backward_planes(ops, name, pair):
         ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=DEV)
         assert lib.wdno_attn_fwd_amax(p(qkv), p(cos), p(sin), p(bias), p(out32), None, C.byref(d), R.SCALE, st) == 0
         assert lib.wdno_attn_bwd_amax(p(qkv), p(cos), p(sin), p(bias), p(out32), p(dout), p(dqkv32), p(db32), None, C.byref(d), R.SCALE, p(ws), nb, st) == 0
-        assert lib.wdno_attn_bwd_planes(p(qkv), p(cos), p(sin), p(bias), p(out32), p(dout), p(hi), p(lo), p(sc), p(db), p(_rec_of(ops, qkv)),
-                                        p(_rec_of(ops, dout)), C.byref(d), R.SCALE, p(ws), nb, st) == 0
+        rq, rd = _rec_of(ops, qkv), _rec_of(ops, dout)                     # (held: two temporaries can be given the same block, one after the other)
+        assert lib.wdno_attn_bwd_planes(p(qkv), p(cos), p(sin), p(bias), p(out32), p(dout), p(hi), p(lo), p(sc), p(db), p(rq), p(rd), C.byref(d),
+                                        R.SCALE, p(ws), nb, st) == 0
     torch.cuda.synchronize()
     if c['dbias']:
         assert torch.equal(db, db32)

@@ -1,17 +1,9 @@
-// attention.hip -- attention kernels of the two U-Nets (head dim fixed at 32, as in the reference).
-//
-//  * softmax attention over short token axes (temporal: 24/48 frames with rotary + relative-position bias;
-//    spatial mid-block: 64/100/400 tokens): one wavefront per (unit, head), K/V staged in LDS, rows streamed.
-//    HBM-bound (no reuse at n = 24); QK^T / PV are far too small to feed MFMA tiles.
-//  * linear attention (softmax over the 32 head channels for q, over all tokens for k): the 32x32 context
-//    k^T v is a genuine dense contraction over thousands of tokens -> v_mfma_f32_32x32x2_f32, streamed from
-//    global memory (each lane supplies one k and one v element per MFMA); the per-token 32x32 mat-vecs run
-//    on the vector ALU with the context broadcast from LDS.
-#include "attn_fused.h"      // tf_key: the key / feature an accumulator register of a lane half holds
+// attention.hip -- softmax attention of the two U-Nets (head dim fixed at 32, as in the reference) over short token axes
+// (temporal: 24/48 frames with rotary + relative-position bias; spatial mid-block: 64/100/400 tokens): one wavefront per
+// (unit, head), K/V staged in LDS, rows streamed. HBM-bound (no reuse at n = 24); QK^T / PV are far too small to feed MFMA tiles.
+// The lane-level steps the kernels share with each other and with linear attention (linattn.hip) are in attn_tiles.h.
+#include "attn_tiles.h"
 #include "debug_modes.h"
-
-#define DH 32
-#define KST 33
 
 // ================================================================================================ softmax attention
 // One THREAD per (unit, head, query row). The rotated K rows of an item live in LDS (every thread of the item reads the
@@ -32,39 +24,6 @@ struct AttnP {
   // dout the scale bound is derived from, and where the scale is left
   _Float16* pl_hi; _Float16* pl_lo; const float* rec_qkv; const float* rec_dout; float* pl_scale;
 };
-// dqkv as planes: store 4 consecutive values of row `row` (element offset inside the [rows][RW] tensor)
-__device__ __forceinline__ void am_store4_planes(_Float16* hi, _Float16* lo, int64_t off, float4 v, float s) {
-  typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-  const float t[4] = {v.x, v.y, v.z, v.w};
-  half4v h, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { _Float16 th, tl; plane_pack(t[j], s, lo == nullptr, th, tl); h[j] = th; l[j] = tl; }
-  *reinterpret_cast<half4v*>(hi + off) = h;
-  if (lo) *reinterpret_cast<half4v*>(lo + off) = l;
-}
-// The MFMA accumulator layout gives lane (li, hh) the channel runs 8 e4 + 4 hh + (0..3) of its row: 8-byte plane stores. One
-// v_permlane32_swap per component trades the odd run of the low half-wave for the even run of the high one (tools/probes/swap_probe.hip),
-// after which a lane owns 8 CONSECUTIVE channels (16 j + 8 hh + 0..7) of each pair j: 16-byte stores. v[e4] = the four runs; off0 = element
-// offset of channel 0 of this head in the lane's row. Both lanes of a pair (l, l + 32) must be active.
-__device__ __forceinline__ void am_store_row_planes(_Float16* hi, _Float16* lo, int64_t off0, int hh, const float4* v, float s) {
-  typedef _Float16 half8v __attribute__((ext_vector_type(8)));
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const float a[4] = {v[2 * j].x, v[2 * j].y, v[2 * j].z, v[2 * j].w}, b[4] = {v[2 * j + 1].x, v[2 * j + 1].y, v[2 * j + 1].z, v[2 * j + 1].w};
-    float t[8];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[c]), __float_as_uint(b[c]), false, false);
-      t[c] = __uint_as_float(r[0]); t[4 + c] = __uint_as_float(r[1]);
-    }
-    half8v h, l;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { _Float16 th, tl; plane_pack(t[c], s, lo == nullptr, th, tl); h[c] = th; l[c] = tl; }
-    const int64_t off = off0 + 16 * j + 8 * hh;
-    *reinterpret_cast<half8v*>(hi + off) = h;
-    if (lo) *reinterpret_cast<half8v*>(lo + off) = l;
-  }
-}
 
 #define ATT_THREADS 256
 #define ATT_BWD_THREADS 128
@@ -112,10 +71,9 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(const float* __re
   const int i0 = threadIdx.x - il * n;            // first row of this thread
   const int64_t item = (int64_t)blockIdx.x * p.ipb + il;
   const bool active = il < p.ipb && item < p.n_items;
-  const int h = active ? (int)(item % p.d.heads) : 0;
-  const int64_t unit = active ? item / p.d.heads : 0;
-  const int uo = (int)(unit / p.d.n_ui), ui = (int)(unit - (int64_t)uo * p.d.n_ui);
-  const int64_t row0 = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si;
+  const AmItem w = am_item(p.d, item, active);
+  const int h = w.h;
+  const int64_t row0 = w.row0;
   float* Ks = smem + (active ? il : 0) * p.kst;
   const int rstep = p.ipb > 1 ? n : ATT_THREADS;  // ipb == 1: threads stride over rows
   if (active) {
@@ -186,11 +144,9 @@ __global__ __launch_bounds__(ATT_BWD_THREADS) void attn_bwd_kernel(const float* 
   for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int64_t item = grp * p.ipb + il;
     const bool active = slot_ok && item < p.n_items;
-    const int h = active ? (int)(item % p.d.heads) : 0;
-    const int64_t unit = active ? item / p.d.heads : 0;
-    const int uo = (int)(unit / p.d.n_ui), ui = (int)(unit - (int64_t)uo * p.d.n_ui);
-    const int64_t row = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si + (int64_t)i * p.d.st;
-    const int64_t row0 = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si;
+    const AmItem w = am_item(p.d, item, active);
+    const int h = w.h;
+    const int64_t row0 = w.row0, row = row0 + (int64_t)i * p.d.st;
     float q[DH];
     __syncthreads();                                  // previous group's phase B is done with the LDS matrices
     if (active) {
@@ -310,10 +266,9 @@ __global__ __launch_bounds__(ATT_BIG_THREADS) void attn_bwd_big_kernel(const flo
   float* Ls = Ms + n;                                 // [n] 1 / row sum
   float* Dl = Ls + n;                                 // [n] delta
   for (int64_t item = blockIdx.x; item < p.n_items; item += gridDim.x) {
-    const int h = (int)(item % p.d.heads);
-    const int64_t unit = item / p.d.heads;
-    const int uo = (int)(unit / p.d.n_ui), ui = (int)(unit - (int64_t)uo * p.d.n_ui);
-    const int64_t row0 = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si;
+    const AmItem w = am_item(p.d, item);
+    const int h = w.h;
+    const int64_t row0 = w.row0;
     __syncthreads();                                  // the previous item's phase B has finished with the statistics
     for (int j = threadIdx.x; j < n; j += ATT_BIG_THREADS) {
       float k[DH], v[DH];
@@ -445,91 +400,9 @@ __global__ __launch_bounds__(256) void attn_dbias_reduce_kernel(const float* __r
 //   O^T[d][i] = sum_j V[j][d] P[i][j]     the reduction index runs over the keys in exactly the order the accumulator holds
 //   them (step m <-> e = m), so P^T feeds the second MFMA without moving data; V is read as coalesced 128-byte rows.
 // The backward needs P and dS with the roles of the lanes swapped (lane = key) for dK / dV: two 32x33 tiles per wave in LDS.
-#define AM_WAVES 4
 #ifndef ATT_BWD_BLOCKS_PER_CU
 #define ATT_BWD_BLOCKS_PER_CU 3      /* 4 (128 registers, 22 spilled): 457 / 139 / 70 us vs 458 / 126 / 75 at hw = 1600 / 400 / 100: no gain */
 #endif
-// wave-uniform pointer in SGPRs: the per-lane part of an address stays a 32-bit offset (global_load saddr + voffset)
-__device__ __forceinline__ const float* am_uniform(const float* p) {
-  uint64_t a = reinterpret_cast<uint64_t>(p);
-  unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  return reinterpret_cast<const float*>(((uint64_t)hi << 32) | lo);
-}
-
-// Rows of one operand ([n][32] floats: q, k, v or dO of one head) -> LDS tile [32][AM_TS], loaded cooperatively (8 lanes
-// per 128-byte row, three passes for 24 rows), optionally scaled and rotated on the way; rows >= n are zero-filled.
-#define AM_TS 36
-template <int NIF = 4>
-__device__ __forceinline__ void am_stage_rows(float* __restrict__ tile, const float* __restrict__ ubase, unsigned row_stride,
-                                              const float* __restrict__ rc, const float* __restrict__ rs, float scale, int n, int lane) {
-  // ubase: wave-uniform pointer to row 0 of the operand (am_uniform); the per-lane part of every address is a 32-bit offset,
-  // so nothing 64-bit per lane has to stay live across the item loop
-  // NIF of the four 1-KiB row groups are requested together (4 KB in flight per wave; one at a time, sixteen waves per CU keep only
-  // ~4 MB in flight chip-wide and the kernel sits at a latency-bound 2.9 TB/s); the rotation tables are fetched pass by pass.
-  // NIF = 2 halves the staging registers where the caller is short of them.
-#pragma unroll
-  for (int k0 = 0; k0 < 4; k0 += NIF) {
-    float4 xs[NIF];
-#pragma unroll
-    for (int k = 0; k < NIF; ++k) {
-      const int idx = lane + 64 * (k0 + k);
-      const int r = idx >> 3, c4 = (idx & 7) * 4;
-      xs[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < n) xs[k] = *reinterpret_cast<const float4*>(ubase + ((unsigned)r * row_stride + (unsigned)c4));
-    }
-#pragma unroll
-    for (int k = 0; k < NIF; ++k) {
-      const int idx = lane + 64 * (k0 + k);
-      const int r = idx >> 3, c4 = (idx & 7) * 4;
-      float4 x = xs[k];
-      x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale;
-      if (rc && r < n) {
-        const float4 c = *reinterpret_cast<const float4*>(rc + r * DH + c4), sn = *reinterpret_cast<const float4*>(rs + r * DH + c4);
-        x = make_float4(x.x * c.x - x.y * sn.x, x.y * c.y + x.x * sn.y, x.z * c.z - x.w * sn.z, x.w * c.w + x.z * sn.w);
-      }
-      *reinterpret_cast<float4*>(tile + r * AM_TS + c4) = x;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-// the 16 values of row `li` this lane feeds to the MFMA steps of a product that contracts over the 32 channels: step m takes the
-// channel pair (m, 16 + m), i.e. lane half hh holds channels d = 16 hh + m -- 16 CONSECUTIVE floats, four conflict-free ds_read_b128
-// (any pairing of channels into steps is valid as long as both operands use it; the first version, d = 2 m + hh, needed sixteen
-// ds_read_b32 at a row stride of 36 floats = 4-way bank conflicts, a fifth of the temporal-attention kernels' LDS cycles)
-#define AM_D(m, hh) (16 * (hh) + (m))
-__device__ __forceinline__ void am_sel(const float* __restrict__ tile, int li, int hh, float* sel) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float4 v = *reinterpret_cast<const float4*>(tile + li * AM_TS + 16 * hh + 4 * q);
-    sel[4 * q] = v.x; sel[4 * q + 1] = v.y; sel[4 * q + 2] = v.z; sel[4 * q + 3] = v.w;
-  }
-}
-// four of them (steps 4 g .. 4 g + 3)
-__device__ __forceinline__ void am_sel4(const float* __restrict__ tile, int li, int hh, int g, float* sel) {
-  const float4 v = *reinterpret_cast<const float4*>(tile + li * AM_TS + 16 * hh + 4 * g);
-  sel[0] = v.x; sel[1] = v.y; sel[2] = v.z; sel[3] = v.w;
-}
-// softmax over the keys of query `li` from the transposed score tile (masked beyond n); returns P^T in place
-__device__ __forceinline__ void am_softmax(f32x16& sT, const float* __restrict__ brow, int n, int hh, bool tok) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int j = tf_key(e, hh);
-    float v = sT[e];
-    if (brow && tok && j < n) v += brow[j];
-    v = j < n ? v : -INFINITY;
-    sT[e] = v;
-    mx = fmaxf(mx, v);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
-  float l = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) { sT[e] = expf(sT[e] - mx); l += sT[e]; }
-  l += __shfl_xor(l, 32);
-  const float inv = 1.0f / l;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) sT[e] *= inv;
-}
 
 // NT: the token count as a compile-time constant (24 frames: every temporal attention of the base models) or 0 = p.d.n_tok. With a
 // constant n every row / key guard below folds (row groups are 8 rows, keys come in runs of 4 per lane half): the generic kernel spends
@@ -553,43 +426,28 @@ __global__ __launch_bounds__(64 * AM_WAVES, 4) void attn_fwd_mfma_kernel(const f
   float* Tq = tiles[wave][0];
   float* Tk = tiles[wave][1];
   for (int64_t item = (int64_t)blockIdx.x * AM_WAVES + wave; item < p.n_items; item += (int64_t)gridDim.x * AM_WAVES) {
-    const int h = (int)(item % p.d.heads);
-    const int64_t unit = item / p.d.heads;
-    const int uo = (int)(unit / p.d.n_ui), ui = (int)(unit - (int64_t)uo * p.d.n_ui);
-    const int64_t row0 = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si;
-    const int64_t rowl = row0 + (int64_t)(tok ? li : 0) * p.d.st;
-    const float* qb = am_uniform(qkv + row0 * p.RW + h * DH);          // q of token 0 of this item; k at + HD, v at + 2 HD
+    const AmItem w = am_item(p.d, item);
+    const int h = w.h;
+    const int64_t rowl = w.row0 + (int64_t)(tok ? li : 0) * p.d.st;
+    const float* qb = am_uniform(qkv + w.row0 * p.RW + h * DH);          // q of token 0 of this item; k at + HD, v at + 2 HD
     const unsigned tstride = (unsigned)(p.d.st * p.RW);
     am_stage_rows(Tq, qb, tstride, rcos, rsin, p.scale, n, lane);
     am_stage_rows(Tk, qb + p.HD, tstride, rcos, rsin, 1.0f, n, lane);
-    // V elements for the second product: step m needs V[key(m, hh)][d = li] (coalesced 128-byte rows)
     float va[16];
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const int j = tf_key(m, hh);
-      va[m] = j < n ? qb[(unsigned)j * tstride + (unsigned)(2 * p.HD + li)] : 0.f;
-    }
+    am_col16(qb, tstride, 0, (unsigned)(2 * p.HD + li), n, hh, 1.0f, va);
     __builtin_amdgcn_wave_barrier();
     float qs[16], ks[16];
     am_sel(Tq, li, hh, qs);
     am_sel(Tk, li, hh, ks);
-    f32x16 sT;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) sT[e] = 0.f;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) sT = __builtin_amdgcn_mfma_f32_32x32x2f32(ks[m], qs[m], sT, 0, 0, 0);
+    f32x16 sT = am_mfma16(ks, qs, tf_zero());
     am_softmax(sT, bias ? bias + ((int64_t)h * n + (tok ? li : 0)) * n : nullptr, n, hh, tok);
-    f32x16 oT;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oT[e] = 0.f;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) oT = __builtin_amdgcn_mfma_f32_32x32x2f32(va[m], sT[m], oT, 0, 0, 0);
-    if (tok) {
+    const f32x16 oT = am_mfma16(va, sT, tf_zero());
+    if (tok) {      // (fp32 or planes: see am_store_row)
       float* orow = out + rowl * p.HD + h * DH;
       float4 vv[4];
 #pragma unroll
       for (int e4 = 0; e4 < 4; ++e4) {
-        vv[e4] = make_float4(oT[4 * e4], oT[4 * e4 + 1], oT[4 * e4 + 2], oT[4 * e4 + 3]);
+        vv[e4] = am_quarter(oT, e4);
         if (!p.pl_hi) *reinterpret_cast<float4*>(orow + 8 * e4 + 4 * hh) = vv[e4];
         am = amax4(am, vv[e4]);
       }
@@ -609,7 +467,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_fwd_mfma64_kernel(const
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int n = p.d.n_tok;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, hh = lane >> 5;
-  float fps = 1.0f;
+  float fps = 1.0f;                                  // (as in attn_fwd_mfma_kernel; a shared function costs this kernel 13 vector instructions)
   if (p.pl_hi && p.pl_lo) {
     fps = scale_from_amax(amax_record_read(p.rec_qkv));
     if (blockIdx.x == 0 && threadIdx.x == 0) p.pl_scale[0] = fps;
@@ -618,10 +476,9 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_fwd_mfma64_kernel(const
   float* Tq = smem + wave * (2 * 64 * AM_TS);
   float* Tk = Tq + 64 * AM_TS;
   for (int64_t item = (int64_t)blockIdx.x * AM_WAVES + wave; item < p.n_items; item += (int64_t)gridDim.x * AM_WAVES) {
-    const int h = (int)(item % p.d.heads);
-    const int64_t unit = item / p.d.heads;
-    const int uo = (int)(unit / p.d.n_ui), ui = (int)(unit - (int64_t)uo * p.d.n_ui);
-    const int64_t row0 = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si;
+    const AmItem w = am_item(p.d, item);
+    const int h = w.h;
+    const int64_t row0 = w.row0;
     const float* qb = am_uniform(qkv + row0 * p.RW + h * DH);
     const unsigned tstride = (unsigned)(p.d.st * p.RW);
 #pragma unroll
@@ -632,7 +489,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_fwd_mfma64_kernel(const
       am_stage_rows(Tk + half * 32 * AM_TS, qb + (unsigned)(half * 32) * tstride + p.HD, tstride, rc, rs, 1.0f, n - half * 32, lane);
     }
     // V elements of both key tiles: step m of tile jt needs V[32 jt + key(m, hh)][d = li]
-    float va[2][16];
+    float va[2][16];      // (am_col16 per tile changes the address code of this kernel: 30 vector instructions)
 #pragma unroll
     for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
@@ -653,12 +510,10 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_fwd_mfma64_kernel(const
       for (int jt = 0; jt < 2; ++jt) {
         float ks[16];
         am_sel(Tk + jt * 32 * AM_TS, li, hh, ks);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sT[jt][e] = 0.f;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) sT[jt] = __builtin_amdgcn_mfma_f32_32x32x2f32(ks[m], qs[m], sT[jt], 0, 0, 0);
+        sT[jt] = am_mfma16(ks, qs, tf_zero());
       }
-      // softmax over the 64 keys of query qi: 32 in this lane (two tiles x 16), 32 in lane ^ 32
+      // softmax over the 64 keys of query qi: 32 in this lane (two tiles x 16), 32 in lane ^ 32; 1 / sum applied at the operand.
+      // The masked maximum stays inline: as am_masked_max over two tiles the bias adds compile to 170 more vector instructions.
       const float* brow = bias ? bias + ((int64_t)h * n + (tok ? qi : 0)) * n : nullptr;
       float mx = -INFINITY;
 #pragma unroll
@@ -673,28 +528,20 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_fwd_mfma64_kernel(const
           mx = fmaxf(mx, v);
         }
       mx = fmaxf(mx, __shfl_xor(mx, 32));
-      float l = 0.f;
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { sT[jt][e] = expf(sT[jt][e] - mx); l += sT[jt][e]; }
-      l += __shfl_xor(l, 32);
-      const float inv = 1.0f / l;
-      f32x16 oT;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) oT[e] = 0.f;
+      const float inv = 1.0f / am_exp_sum<2>(sT, mx);
+      f32x16 oT = tf_zero();
 #pragma unroll
       for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
         for (int m = 0; m < 16; ++m) oT = __builtin_amdgcn_mfma_f32_32x32x2f32(va[jt][m], sT[jt][m] * inv, oT, 0, 0, 0);
       // both lanes of a pair (l, l + 32) hold the same query, so `tok` is uniform over the pair (am_store_row_planes needs that)
-      if (tok) {
+      if (tok) {      // (fp32 or planes: see am_store_row)
         const int64_t rowl = row0 + (int64_t)qi * p.d.st;
         float* orow = out + rowl * p.HD + h * DH;
         float4 vv[4];
 #pragma unroll
         for (int e4 = 0; e4 < 4; ++e4) {
-          vv[e4] = make_float4(oT[4 * e4], oT[4 * e4 + 1], oT[4 * e4 + 2], oT[4 * e4 + 3]);
+          vv[e4] = am_quarter(oT, e4);
           if (!p.pl_hi) *reinterpret_cast<float4*>(orow + 8 * e4 + 4 * hh) = vv[e4];
           am = amax4(am, vv[e4]);
         }
@@ -721,72 +568,41 @@ __global__ __launch_bounds__(64 * AM_WAVES, 3) void attn_fwd_mfma_tiled_kernel(c
   for (int64_t wk = (int64_t)blockIdx.x * AM_WAVES + wave; wk < nwork; wk += (int64_t)gridDim.x * AM_WAVES) {
     const int64_t item = wk / ntile;
     const int it = (int)(wk - item * ntile);
-    const int h = (int)(item % p.d.heads);
-    const int64_t unit = item / p.d.heads;
-    const int uo = (int)(unit / p.d.n_ui), ui = (int)(unit - (int64_t)uo * p.d.n_ui);
-    const int64_t row0 = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si;
-    const float* qb = am_uniform(qkv + row0 * p.RW + h * DH);          // q of token 0 of this item; k at + HD, v at + 2 HD
+    const AmItem w = am_item(p.d, item);
+    const int h = w.h;
+    const float* qb = am_uniform(qkv + w.row0 * p.RW + h * DH);          // q of token 0 of this item; k at + HD, v at + 2 HD
     const int qi = 32 * it + li;
     const bool tok = qi < n;
     float qs[16];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float4 v4 = tok ? *reinterpret_cast<const float4*>(qb + (unsigned)qi * tstride + 8 * c + 4 * hh) : make_float4(0.f, 0.f, 0.f, 0.f);
-      qs[4 * c] = v4.x * p.scale; qs[4 * c + 1] = v4.y * p.scale; qs[4 * c + 2] = v4.z * p.scale; qs[4 * c + 3] = v4.w * p.scale;
-    }
-    f32x16 oT;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oT[e] = 0.f;
+    am_row16(qb + (unsigned)qi * tstride, hh, tok, p.scale, qs);
+    f32x16 oT = tf_zero();
     float m_run = -INFINITY, l_run = 0.f;
 #pragma unroll 1
     for (int jt = 0; jt < ntile; ++jt) {
       const int kj = 32 * jt + li;
       float ks[16], va[16];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
+      for (int c = 0; c < 4; ++c) {      // (am_row16 with HD in the pointer: other address code, 10 vector instructions)
         const float4 v4 = kj < n ? *reinterpret_cast<const float4*>(qb + (unsigned)kj * tstride + (unsigned)(p.HD + 8 * c + 4 * hh)) : make_float4(0.f, 0.f, 0.f, 0.f);
         ks[4 * c] = v4.x; ks[4 * c + 1] = v4.y; ks[4 * c + 2] = v4.z; ks[4 * c + 3] = v4.w;
       }
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const int j = 32 * jt + tf_key(m, hh);
-        va[m] = j < n ? qb[(unsigned)j * tstride + (unsigned)(2 * p.HD + li)] : 0.f;
-      }
-      f32x16 sT;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) sT[e] = 0.f;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) sT = __builtin_amdgcn_mfma_f32_32x32x2f32(ks[m], qs[m], sT, 0, 0, 0);
-      float mx = -INFINITY;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const float v = 32 * jt + tf_key(e, hh) < n ? sT[e] : -INFINITY;
-        sT[e] = v;
-        mx = fmaxf(mx, v);
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      am_col16(qb, tstride, 32 * jt, (unsigned)(2 * p.HD + li), n, hh, 1.0f, va);
+      f32x16 sT = am_mfma16(ks, qs, tf_zero());
+      // the online update: the running maximum joins the tile's before the exponentials are taken
+      const float mx = am_masked_max(sT, nullptr, 32 * jt, n, hh, tok);
       const float m_new = fmaxf(m_run, mx);                       // finite: every key tile holds at least one key
       const float corr = expf(m_run - m_new);                     // (0 for the first tile)
-      float l = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { sT[e] = expf(sT[e] - m_new); l += sT[e]; }
-      l += __shfl_xor(l, 32);
-      l_run = l_run * corr + l;
+      l_run = l_run * corr + am_exp_sum<1>(&sT, m_new);
       m_run = m_new;
 #pragma unroll
       for (int e = 0; e < 16; ++e) oT[e] *= corr;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) oT = __builtin_amdgcn_mfma_f32_32x32x2f32(va[m], sT[m], oT, 0, 0, 0);
+      oT = am_mfma16(va, sT, oT);
     }
     if (tok) {
       const float inv = 1.0f / l_run;
-      float* orow = out + (row0 + (int64_t)qi * p.d.st) * p.HD + h * DH;
 #pragma unroll
-      for (int e4 = 0; e4 < 4; ++e4) {
-        const float4 vv = make_float4(oT[4 * e4] * inv, oT[4 * e4 + 1] * inv, oT[4 * e4 + 2] * inv, oT[4 * e4 + 3] * inv);
-        *reinterpret_cast<float4*>(orow + 8 * e4 + 4 * hh) = vv;
-        am = amax4(am, vv);
-      }
+      for (int e = 0; e < 16; ++e) oT[e] *= inv;
+      am_store_row(oT, out + (w.row0 + (int64_t)qi * p.d.st) * p.HD + h * DH, hh, am);
     }
   }
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * AM_WAVES + wave);
@@ -815,10 +631,9 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
   const unsigned tq = (unsigned)(p.d.st * p.RW), to = (unsigned)(p.d.st * p.HD);
   float am = 0.f;
   for (int64_t item = blockIdx.x; item < p.n_items; item += gridDim.x) {
-    const int h = (int)(item % p.d.heads);
-    const int64_t unit = item / p.d.heads;
-    const int uo = (int)(unit / p.d.n_ui), ui = (int)(unit - (int64_t)uo * p.d.n_ui);
-    const int64_t row0 = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si;
+    const AmItem w = am_item(p.d, item);
+    const int h = w.h;
+    const int64_t row0 = w.row0;
     const float* qb = am_uniform(qkv + row0 * p.RW + h * DH);           // q of token 0; k at + HD, v at + 2 HD
     const float* gb = am_uniform(dout + row0 * p.HD + h * DH);
     const float* ob = am_uniform(fout + row0 * p.HD + h * DH);
@@ -830,12 +645,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
     };
     auto row16 = [&](const float* base, unsigned stride, int t, unsigned col0, float mul, float (&v)[16]) {
       if (STAGED) {
-        const float* T = tile_of(base, col0) + t * ATT_TILED_TS;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float4 v4 = *reinterpret_cast<const float4*>(T + 8 * c + 4 * hh);
-          v[4 * c] = v4.x; v[4 * c + 1] = v4.y; v[4 * c + 2] = v4.z; v[4 * c + 3] = v4.w;
-        }
+        am_row16(tile_of(base, col0) + t * ATT_TILED_TS, hh, true, 1.0f, v);
         return;
       }
 #pragma unroll
@@ -852,11 +662,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
         for (int m = 0; m < 16; ++m) v[m] = T[tf_key(m, hh) * ATT_TILED_TS];
         return;
       }
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const int t = t0 + tf_key(m, hh);
-        v[m] = t < n ? base[(unsigned)t * stride + col0 + li] * mul : 0.f;
-      }
+      am_col16(base, stride, t0, col0 + li, n, hh, mul, v);
     };
     __syncthreads();                                  // the previous item's phase B has finished with the statistics (and the tiles)
     if (STAGED) {                                     // 4 tiles x 128 rows x 8 chunks of 16 bytes; q scaled here; rows beyond n zero
@@ -891,19 +697,10 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
       for (int jt = 0; jt < ntile; ++jt) {
         float ks[16];
         row16(qb, tq, 32 * jt + li, p.HD, 1.0f, ks);
-        f32x16 sT;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sT[e] = 0.f;
+        f32x16 sT = tf_zero();
 #pragma unroll
         for (int m = 0; m < 16; ++m) sT = __builtin_amdgcn_mfma_f32_32x32x2f32(ks[m], qs[m], sT, 0, 0, 0);
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const float v = 32 * jt + tf_key(e, hh) < n ? sT[e] : -INFINITY;
-          sT[e] = v;
-          mx = fmaxf(mx, v);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float mx = am_masked_max(sT, nullptr, 32 * jt, n, hh, true);
         const float m_new = fmaxf(m_run, mx);
         float l = 0.f;
 #pragma unroll
@@ -913,14 +710,10 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
         m_run = m_new;
       }
       const float inv_l = 1.0f / l_run;
-      f32x16 dqT;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) dqT[e] = 0.f;
+      f32x16 dqT = tf_zero();
 #pragma unroll 1
       for (int jt = 0; jt < ntile; ++jt) {
-        f32x16 sT, dpT;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { sT[e] = 0.f; dpT[e] = 0.f; }
+        f32x16 sT = tf_zero(), dpT = tf_zero();
         {
           float ks[16], vs[16];
           row16(qb, tq, 32 * jt + li, p.HD, 1.0f, ks);
@@ -939,19 +732,14 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
         {
           float kc[16];
           col16(qb, tq, 32 * jt, p.HD, 1.0f, kc);
-#pragma unroll
-          for (int m = 0; m < 16; ++m) dqT = __builtin_amdgcn_mfma_f32_32x32x2f32(kc[m], sT[m], dqT, 0, 0, 0);
+          dqT = am_mfma16(kc, sT, dqT);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
       if (qi < n) {
-        float* dr = db + (unsigned)qi * tq;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float4 vv = make_float4(dqT[4 * c] * p.scale, dqT[4 * c + 1] * p.scale, dqT[4 * c + 2] * p.scale, dqT[4 * c + 3] * p.scale);
-          *reinterpret_cast<float4*>(dr + 8 * c + 4 * hh) = vv;
-          am = amax4(am, vv);
-        }
+        for (int e = 0; e < 16; ++e) dqT[e] *= p.scale;
+        am_store_row(dqT, db + (unsigned)qi * tq, hh, am);
         if (hh == 0) { Ms[qi] = m_run; Ls[qi] = inv_l; Dl[qi] = delta; }
       }
     }
@@ -963,18 +751,14 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
       float kb[16], vb[16];
       row16(qb, tq, kj, p.HD, 1.0f, kb);
       row16(qb, tq, kj, 2 * p.HD, 1.0f, vb);
-      f32x16 dkT, dvT;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { dkT[e] = 0.f; dvT[e] = 0.f; }
+      f32x16 dkT = tf_zero(), dvT = tf_zero();
 #pragma unroll 1
       for (int it = 0; it < ntile; ++it) {
-        f32x16 S, dP;
+        f32x16 S = tf_zero(), dP = tf_zero();
         {
           float qa[16], ga[16];
           row16(qb, tq, 32 * it + li, 0, p.scale, qa);
           row16(gb, to, 32 * it + li, 0, 1.0f, ga);
-#pragma unroll
-          for (int e = 0; e < 16; ++e) { S[e] = 0.f; dP[e] = 0.f; }
 #pragma unroll
           for (int m = 0; m < 16; ++m) S = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[m], kb[m], S, 0, 0, 0);
 #pragma unroll
@@ -1015,34 +799,14 @@ __global__ __launch_bounds__(64 * AM_WAVES, 2) void attn_bwd_mfma_tiled_kernel(c
       }
       if (kj < n) {
         float* dr = db + (unsigned)kj * tq;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float4 kk = make_float4(dkT[4 * c], dkT[4 * c + 1], dkT[4 * c + 2], dkT[4 * c + 3]);
-          const float4 vv = make_float4(dvT[4 * c], dvT[4 * c + 1], dvT[4 * c + 2], dvT[4 * c + 3]);
-          *reinterpret_cast<float4*>(dr + p.HD + 8 * c + 4 * hh) = kk;
-          *reinterpret_cast<float4*>(dr + 2 * p.HD + 8 * c + 4 * hh) = vv;
-          am = amax4(amax4(am, kk), vv);
-        }
+        am_store_row(dkT, dr + p.HD, hh, am);
+        am_store_row(dvT, dr + 2 * p.HD, hh, am);
       }
     }
   }
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * AM_WAVES + wave);
 }
 
-// element (row j, channel li) of a rotated q / k row, read column-wise (coalesced 128-byte rows): the rotation partner sits in
-// the neighbouring lane
-__device__ __forceinline__ float am_rot_elem(float x, const float* __restrict__ rc, const float* __restrict__ rs, int j, int li, bool ok) {
-  if (!rc) return x;
-  const float partner = __shfl_xor(x, 1);
-  const float c = ok ? rc[j * DH + li] : 1.f, sn = ok ? rs[j * DH + li] : 0.f;
-  return (li & 1) ? x * c + partner * sn : x * c - partner * sn;
-}
-// gradient of the rotation on a run of four consecutive channels d0..d0+3 held by one lane (pairs are inside the run)
-__device__ __forceinline__ float4 am_unrotate4(float4 g, const float* __restrict__ rc, const float* __restrict__ rs, int d0) {
-  if (!rc) return g;
-  const float4 c = *reinterpret_cast<const float4*>(rc + d0), s = *reinterpret_cast<const float4*>(rs + d0);
-  return make_float4(g.x * c.x + g.y * s.x, g.y * c.y - g.x * s.y, g.z * c.z + g.w * s.z, g.w * c.w - g.z * s.w);
-}
 
 template <int NT>
 __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ rcos,
@@ -1066,9 +830,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
   // (p.db_slices) every wave owns a partial [heads][n][n] of its own and the block adds the four in wave order at the end.
   const bool db_regs = dbias && p.d.heads == AM_WAVES;
   float* dBw = dBs + (p.db_slices ? (size_t)wave * p.d.heads * n * n : 0);
-  f32x16 dbacc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) dbacc[e] = 0.f;
+  f32x16 dbacc = tf_zero();
   if (dbias && !db_regs) {
     for (int e = threadIdx.x; e < (p.db_slices ? AM_WAVES : 1) * p.d.heads * n * n; e += 64 * AM_WAVES) dBs[e] = 0.f;
     __syncthreads();
@@ -1085,10 +847,9 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
     if (blockIdx.x == 0 && threadIdx.x == 0) p.pl_scale[0] = ps;
   }
   for (int64_t item = (int64_t)blockIdx.x * AM_WAVES + wave; item < p.n_items; item += (int64_t)gridDim.x * AM_WAVES) {
-    const int h = (int)(item % p.d.heads);
-    const int64_t unit = item / p.d.heads;
-    const int uo = (int)(unit / p.d.n_ui), ui = (int)(unit - (int64_t)uo * p.d.n_ui);
-    const int64_t row0 = (int64_t)uo * p.d.so + (int64_t)ui * p.d.si;
+    const AmItem w = am_item(p.d, item);
+    const int h = w.h;
+    const int64_t row0 = w.row0;
     const float* qb = am_uniform(qkv + row0 * p.RW + h * DH);          // q of token 0 of this item; k at + HD, v at + 2 HD
     const float* gb = am_uniform(dout + row0 * p.HD + h * DH);
     const float* fb = am_uniform(fout + row0 * p.HD + h * DH);
@@ -1109,16 +870,13 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
       am_stage_rows(Ta, qb + 2 * p.HD, tstride, nullptr, nullptr, 1.0f, n, lane);
       am_stage_rows(Tb, gb, gstride, nullptr, nullptr, 1.0f, n, lane);
       __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int e = 0; e < 16; ++e) dsT[e] = 0.f;
+      dsT = tf_zero();
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {          // four steps at a time: bounded live registers (the kernel runs at 128 VGPRs)
         float va[4], gg[4];
         am_sel4(Ta, li, hh, g4, va);
         am_sel4(Tb, li, hh, g4, gg);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dsT = __builtin_amdgcn_mfma_f32_32x32x2f32(va[q], gg[q], dsT, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        dsT = am_mfma4(va, gg, dsT);
       }
     }
     {
@@ -1126,16 +884,13 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
       am_stage_rows<2>(Ta, qb, tstride, rcos, rsin, p.scale, n, lane);
       am_stage_rows<2>(Tb, qb + p.HD, tstride, rcos, rsin, 1.0f, n, lane);
       __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int e = 0; e < 16; ++e) pT[e] = 0.f;
+      pT = tf_zero();
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         float qa[4], kb[4];
         am_sel4(Ta, li, hh, g4, qa);
         am_sel4(Tb, li, hh, g4, kb);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) pT = __builtin_amdgcn_mfma_f32_32x32x2f32(kb[q], qa[q], pT, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        pT = am_mfma4(kb, qa, pT);
       }
       am_softmax(pT, bias ? bias + ((int64_t)h * n + (tok ? li : 0)) * n : nullptr, n, hh, tok);
       // delta_i = <dO_i, O_i> = sum_j P_ij dP_ij: both factors are in this lane's accumulators (16 keys here, 16 in lane ^ 32; masked
@@ -1149,9 +904,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
     }
     // dQ^T[d][i] = sum_j K[j][d] dS^T[j][i]: K columns from the staged (rotated) tile, dS^T straight from the accumulator
     {
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+      f32x16 acc = tf_zero();
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         float ka[4];
@@ -1161,9 +914,8 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
           const unsigned j = (unsigned)(8 * (m >> 2) + (m & 3)) + hz;
           ka[q] = Tb[j * AM_TS + (unsigned)li];        // rows >= n are zero-filled by the staging
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[q], dsT[4 * g4 + q], acc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        const float dg[4] = {dsT[4 * g4], dsT[4 * g4 + 1], dsT[4 * g4 + 2], dsT[4 * g4 + 3]};
+        acc = am_mfma4(ka, dg, acc);
       }
       if (tok) {
         float* drow = db + lrow * tstride;
@@ -1193,9 +945,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
     __builtin_amdgcn_wave_barrier();
     // dK^T[d][j] = sum_i Q[i][d] dS[i][j]: Q columns from the staged (scaled, rotated) tile
     {
-      f32x16 dk;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) dk[e] = 0.f;
+      f32x16 dk = tf_zero();
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         float qa[4];
@@ -1209,9 +959,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
         // bank-conflicted: 36 li mod 64 takes 16 values for 32 lanes)
         const float4 sb4 = *reinterpret_cast<const float4*>(St + li * AM_TS + 8 * g4 + hz);
         const float sb[4] = {sb4.x, sb4.y, sb4.z, sb4.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dk = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[q], sb[q], dk, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        dk = am_mfma4(qa, sb, dk);
       }
       if (tok) {
         float* drow = db + (lrow * tstride + (unsigned)p.HD);
@@ -1233,9 +981,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
     for (int e = 0; e < 16; ++e) Pt[tf_key(e, hh) * AM_TS + li] = pT[e];
     __builtin_amdgcn_wave_barrier();
     {
-      f32x16 dv;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) dv[e] = 0.f;
+      f32x16 dv = tf_zero();
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         float ga[4];
@@ -1247,9 +993,7 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
         }
         const float4 pb4 = *reinterpret_cast<const float4*>(Pt + li * AM_TS + 8 * g4 + hz);
         const float pb[4] = {pb4.x, pb4.y, pb4.z, pb4.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dv = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[q], pb[q], dv, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        dv = am_mfma4(ga, pb, dv);
       }
       if (tok) {
         float* drow = db + (lrow * tstride + (unsigned)(2 * p.HD));
@@ -1290,8 +1034,8 @@ __global__ __launch_bounds__(64 * AM_WAVES, ATT_BWD_BLOCKS_PER_CU) void attn_bwd
 #define ATT_ROWS_MAXLDS (160 * 1024)
 static void attn_fwd_mfma64_launch(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
                                    const AttnP& p, int nb, hipStream_t st) {
-  static bool done = false;
-  if (!done) { (void)hipFuncSetAttribute((const void*)attn_fwd_mfma64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_MFMA64_LDS); done = true; }
+  static bool done = false;      // once per process
+  if (!done) { am_dyn_lds((const void*)attn_fwd_mfma64_kernel, ATT_MFMA64_LDS); done = true; }
   attn_fwd_mfma64_kernel<<<(unsigned)nb, 64 * AM_WAVES, ATT_MFMA64_LDS, st>>>(qkv, rot_cos, rot_sin, bias, out, p);
 }
 // Grid of the one-wave-per-item kernels: exactly the blocks that are RESIDENT together (blocks per CU x CUs), each wave walking over
@@ -1441,39 +1185,41 @@ static int attn_fwd_launch(const wdno_attn_plan& pl, const float* qkv, const flo
     case WDNO_ATTN_TILED: attn_fwd_mfma_tiled_kernel<<<(unsigned)pl.grid, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, p); break;
     case WDNO_ATTN_ROWS:
       p.ipb = pl.items_per_block;
-      if (pl.lds_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+      if (pl.lds_bytes > 64 * 1024) am_dyn_lds((const void*)attn_fwd_kernel, pl.lds_bytes);
       attn_fwd_kernel<<<(unsigned)pl.grid, ATT_THREADS, (size_t)pl.lds_bytes, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, p);
       break;
     default: return WDNO_EUNSUPPORTED;
   }
   return wdno_check_launch();
 }
-extern "C" int wdno_attn_fwd_amax(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
-                                  float* amax_rec, const wdno_attn_desc* d, float scale, wdno_stream_t s) {
+// the one body of the forward entry points: fills AttnP, asks the plan. planes: out delivered ONLY as fp16 planes for the to_out projection
+// (MFMA paths only: n_tok <= 64; `out` is not written; out_lo == NULL: one bf16 plane)
+static int attn_fwd_run(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out, float* amax_rec,
+                        const wdno_attn_desc* d, float scale, wdno_stream_t s, bool planes, void* out_hi = nullptr, void* out_lo = nullptr,
+                        float* out_scale = nullptr, const float* rec_qkv = nullptr) {
   AttnP p;
   int rc = attn_fill(p, d, scale, ATT_THREADS);
   if (rc) return rc;
   wdno_attn_plan pl;
-  rc = attn_fwd_choose(d, rot_cos != nullptr, bias != nullptr, false, pl);
+  rc = attn_fwd_choose(d, rot_cos != nullptr, bias != nullptr, planes, pl);
   if (rc) return rc;
-  if (pl.family == WDNO_ATTN_ROWS) return attn_amax_sweep(attn_fwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, p, s), out, d, p.HD, amax_rec, s);
+  if (planes) {
+    if (!out_hi || (out_lo && (!out_scale || !rec_qkv))) return WDNO_EUNSUPPORTED;
+    p.pl_hi = (_Float16*)out_hi; p.pl_lo = (_Float16*)out_lo; p.rec_qkv = rec_qkv; p.pl_scale = out_scale;
+  } else if (pl.family == WDNO_ATTN_ROWS) {
+    return attn_amax_sweep(attn_fwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, p, s), out, d, p.HD, amax_rec, s);
+  }
   p.amax_rec = amax_rec;
   return attn_fwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, p, s);
 }
-// forward with out delivered ONLY as fp16 planes for the to_out projection (MFMA paths only: n_tok <= 64; `out` is not written)
+extern "C" int wdno_attn_fwd_amax(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
+                                  float* amax_rec, const wdno_attn_desc* d, float scale, wdno_stream_t s) {
+  return attn_fwd_run(qkv, rot_cos, rot_sin, bias, out, amax_rec, d, scale, s, false);
+}
 extern "C" int wdno_attn_fwd_planes(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, float* out,
                                     void* out_hi, void* out_lo, float* out_scale, float* amax_rec, const float* rec_qkv,
                                     const wdno_attn_desc* d, float scale, wdno_stream_t s) {
-  AttnP p;
-  int rc = attn_fill(p, d, scale, ATT_THREADS);
-  if (rc) return rc;
-  wdno_attn_plan pl;
-  rc = attn_fwd_choose(d, rot_cos != nullptr, bias != nullptr, true, pl);
-  if (rc) return rc;
-  if (!out_hi || (out_lo && (!out_scale || !rec_qkv))) return WDNO_EUNSUPPORTED;      // out_lo == NULL: one bf16 plane
-  p.amax_rec = amax_rec;
-  p.pl_hi = (_Float16*)out_hi; p.pl_lo = (_Float16*)out_lo; p.rec_qkv = rec_qkv; p.pl_scale = out_scale;
-  return attn_fwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, p, s);
+  return attn_fwd_run(qkv, rot_cos, rot_sin, bias, out, amax_rec, d, scale, s, true, out_hi, out_lo, out_scale, rec_qkv);
 }
 // blocks of the backward launch with a bias gradient (= number of dbias partials) and the workspace that holds them; none for a shape the
 // backward refuses (the launch paths return that refusal before they look at the workspace)
@@ -1502,779 +1248,56 @@ static int attn_bwd_launch(const wdno_attn_plan& pl, const float* qkv, const flo
   const size_t lds = (size_t)pl.lds_bytes;
   p.db_slices = pl.dbias_in_lds == AM_WAVES;
   if ((pl.family == WDNO_ATTN_MFMA24 || pl.family == WDNO_ATTN_MFMA) && pl.lds_bytes > 64 * 1024)
-    (void)hipFuncSetAttribute(pl.family == WDNO_ATTN_MFMA24 ? (const void*)attn_bwd_mfma_kernel<24> : (const void*)attn_bwd_mfma_kernel<0>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+    am_dyn_lds(pl.family == WDNO_ATTN_MFMA24 ? (const void*)attn_bwd_mfma_kernel<24> : (const void*)attn_bwd_mfma_kernel<0>, lds);
   switch (pl.family) {
     case WDNO_ATTN_MFMA24: attn_bwd_mfma_kernel<24><<<nb, 64 * AM_WAVES, lds, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p); break;
     case WDNO_ATTN_MFMA: attn_bwd_mfma_kernel<0><<<nb, 64 * AM_WAVES, lds, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p); break;
     case WDNO_ATTN_TILED_STAGED: attn_bwd_mfma_tiled_kernel<true><<<nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, dout, dqkv, p); break;
     case WDNO_ATTN_TILED_UNSTAGED: attn_bwd_mfma_tiled_kernel<false><<<nb, 64 * AM_WAVES, 0, as_stream(s)>>>(qkv, out, dout, dqkv, p); break;
     case WDNO_ATTN_BIG:
-      (void)hipFuncSetAttribute((const void*)attn_bwd_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+      am_dyn_lds((const void*)attn_bwd_big_kernel, lds);      // always
       attn_bwd_big_kernel<<<nb, ATT_BIG_THREADS, lds, as_stream(s)>>>(qkv, out, dout, dqkv, p);
       break;
     case WDNO_ATTN_ROWS:
       p.ipb = pl.items_per_block;
-      if (pl.lds_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+      if (pl.lds_bytes > 64 * 1024) am_dyn_lds((const void*)attn_bwd_kernel, lds);
       attn_bwd_kernel<<<nb, ATT_BWD_THREADS, lds, as_stream(s)>>>(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p);
       break;
     default: return WDNO_EUNSUPPORTED;
   }
   return wdno_check_launch();
 }
-extern "C" int wdno_attn_bwd_amax(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out,
-                                  const float* dout, float* dqkv, float* dbias, float* amax_rec, const wdno_attn_desc* d, float scale,
-                                  void* ws, size_t ws_bytes, wdno_stream_t s) {
+// the one body of the backward entry points. planes: dqkv as fp16 planes for the qkv projection's gradient kernels (MFMA path only:
+// n_tok <= 32; dqkv_lo == NULL: one bf16 plane, no scale); the plan is then never one of the two families that need the amax sweep
+static int attn_bwd_run(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out, const float* dout,
+                        float* dqkv, float* dbias, float* amax_rec, const wdno_attn_desc* d, float scale, void* ws, size_t ws_bytes,
+                        wdno_stream_t s, bool planes, void* dqkv_hi = nullptr, void* dqkv_lo = nullptr, float* dqkv_scale = nullptr,
+                        const float* rec_qkv = nullptr, const float* rec_dout = nullptr) {
   AttnP p;
   int rc = attn_fill(p, d, scale, ATT_BWD_THREADS);
   if (rc) return rc;
   wdno_attn_plan pl;
-  rc = attn_bwd_choose(d, rot_cos != nullptr, bias != nullptr, dbias != nullptr, false, out != nullptr, pl);
+  rc = attn_bwd_choose(d, rot_cos != nullptr, bias != nullptr, dbias != nullptr, planes, out != nullptr, pl);
   if (rc) return rc;
+  if (planes && (!dqkv_hi || (dqkv_lo && (!dqkv_scale || !rec_qkv || !rec_dout)))) return WDNO_EUNSUPPORTED;
   if (dbias && (!ws || ws_bytes < wdno_attn_bwd_ws_bytes(d))) return WDNO_EWORKSPACE;
   float* part = dbias ? (float*)ws : nullptr;           // the kernels write per-block partials; the reduce below writes dbias
   const bool sweep = pl.family == WDNO_ATTN_BIG || pl.family == WDNO_ATTN_ROWS;      // these two do not track the amax of what they write
   if (!sweep) p.amax_rec = amax_rec;
+  if (planes) { p.pl_hi = (_Float16*)dqkv_hi; p.pl_lo = (_Float16*)dqkv_lo; p.rec_qkv = rec_qkv; p.rec_dout = rec_dout; p.pl_scale = dqkv_scale; }
   rc = attn_bwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, dout, dqkv, part, p, s);
   if (sweep) rc = attn_amax_sweep(rc, dqkv, d, p.RW, amax_rec, s);
   return (rc || !dbias) ? rc : attn_dbias_reduce(part, pl.dbias_partials, dbias, d, s);
 }
-// dqkv as fp16 planes for the qkv projection's gradient kernels (MFMA path only: n_tok <= 32)
+extern "C" int wdno_attn_bwd_amax(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out,
+                                  const float* dout, float* dqkv, float* dbias, float* amax_rec, const wdno_attn_desc* d, float scale,
+                                  void* ws, size_t ws_bytes, wdno_stream_t s) {
+  return attn_bwd_run(qkv, rot_cos, rot_sin, bias, out, dout, dqkv, dbias, amax_rec, d, scale, ws, ws_bytes, s, false);
+}
 extern "C" int wdno_attn_bwd_planes(const float* qkv, const float* rot_cos, const float* rot_sin, const float* bias, const float* out,
                                     const float* dout, void* dqkv_hi, void* dqkv_lo, float* dqkv_scale, float* dbias,
                                     const float* rec_qkv, const float* rec_dout, const wdno_attn_desc* d, float scale, void* ws, size_t ws_bytes,
                                     wdno_stream_t s) {
-  AttnP p;
-  int rc = attn_fill(p, d, scale, ATT_BWD_THREADS);
-  if (rc) return rc;
-  wdno_attn_plan pl;
-  rc = attn_bwd_choose(d, rot_cos != nullptr, bias != nullptr, dbias != nullptr, true, out != nullptr, pl);
-  if (rc) return rc;
-  if (!dqkv_hi || (dqkv_lo && (!dqkv_scale || !rec_qkv || !rec_dout))) return WDNO_EUNSUPPORTED;      // dqkv_lo == NULL: one bf16 plane, no scale
-  if (dbias && (!ws || ws_bytes < wdno_attn_bwd_ws_bytes(d))) return WDNO_EWORKSPACE;
-  float* part = dbias ? (float*)ws : nullptr;
-  p.pl_hi = (_Float16*)dqkv_hi; p.pl_lo = (_Float16*)dqkv_lo; p.rec_qkv = rec_qkv; p.rec_dout = rec_dout; p.pl_scale = dqkv_scale;
-  rc = attn_bwd_launch(pl, qkv, rot_cos, rot_sin, bias, out, dout, nullptr, part, p, s);
-  return (rc || !dbias) ? rc : attn_dbias_reduce(part, pl.dbias_partials, dbias, d, s);
-}
-
-// ================================================================================================ linear attention
-// pass 1: per (unit, column = head*32+d): max over tokens and sum of exp -> kstats[unit][col][2].
-// A unit has up to 1600 tokens but there are only ~200 units: the token range is cut into `chunks` pieces (one block each,
-// online-softmax partials into a scratch area) and a second tiny launch merges them, so the sweep fills the chip.
-__device__ __forceinline__ void softmax_merge(float& m, float& l, float m2, float l2) {
-  float mn = fmaxf(m, m2);
-  float a = (m == -INFINITY) ? 0.f : l * expf(m - mn);
-  float b = (m2 == -INFINITY) ? 0.f : l2 * expf(m2 - mn);
-  l = a + b; m = mn;
-}
-__global__ __launch_bounds__(256) void linattn_kstats_kernel(const float* __restrict__ qkv, float* __restrict__ part, int n, int HD, int chunks) {
-  __shared__ float rm[256], rl[256];
-  const int unit = blockIdx.x / chunks, chunk = blockIdx.x - unit * chunks;
-  const int per = (n + chunks - 1) / chunks;
-  const int jb = chunk * per, je = min(n, jb + per);
-  const int col = threadIdx.x % HD, rg = threadIdx.x / HD, nrg = 256 / HD;
-  const float* kp = qkv + ((int64_t)unit * n) * (3 * HD) + HD + col;
-  float m = -INFINITY, l = 0.f;
-  // eight rows per round: the loads are requested together and the running sum is rescaled once per round (row by row the
-  // online softmax is a chain of load -> exp -> exp with one 512-byte request in flight per wave)
-  for (int j = jb + rg; j < je; j += 8 * nrg) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = j + u * nrg < je ? kp[(int64_t)(j + u * nrg) * 3 * HD] : -INFINITY;
-    float mn = m;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) mn = fmaxf(mn, v[u]);
-    float add = 0.f;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) add += expf(v[u] - mn);        // exp(-inf) = 0 for the rows past the end
-    l = (m == -INFINITY ? 0.f : l * expf(m - mn)) + add;
-    m = mn;
-  }
-  rm[threadIdx.x] = m; rl[threadIdx.x] = l;
-  __syncthreads();
-  if (rg == 0) {
-    for (int t = 1; t < nrg; ++t) softmax_merge(m, l, rm[t * HD + col], rl[t * HD + col]);
-    part[((int64_t)blockIdx.x * HD + col) * 2 + 0] = m;
-    part[((int64_t)blockIdx.x * HD + col) * 2 + 1] = l;
-  }
-}
-__global__ __launch_bounds__(256) void linattn_kstats_merge_kernel(const float* __restrict__ part, float* __restrict__ kstats, int64_t cols, int HD, int chunks) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // (unit, col)
-  if (i >= cols) return;
-  const int64_t unit = i / HD;
-  const int col = (int)(i - unit * HD);
-  float m = -INFINITY, l = 0.f;
-  for (int c = 0; c < chunks; ++c) {
-    const float* q = part + (((unit * chunks + c) * HD) + col) * 2;
-    softmax_merge(m, l, q[0], q[1]);
-  }
-  kstats[i * 2] = m;
-  kstats[i * 2 + 1] = l;
-}
-
-// pass 2 (MODE 0): ctx[d][e]  = sum_n softmax_n(k)[n][d] * v[n][e]        A = exp(k - m)/l, B = v
-//        (MODE 1): dctx[d][e] = sum_n qs[n][d] * dout[n][e]                A = scale*softmax_d(q), B = dout ; also T[d]
-// one block (4 waves) per (unit, head); every MFMA consumes two tokens.
-template <int MODE>
-__global__ __launch_bounds__(256) void linattn_ctx_kernel(const float* __restrict__ qkv, const float* __restrict__ other,
-                                                           const float* __restrict__ kstats, const float* __restrict__ ctx_in,
-                                                           float* __restrict__ ctx_out, float* __restrict__ tvec,
-                                                           int n, int heads, float scale, int chunks = 1, float* __restrict__ part = nullptr) {
-  // chunks > 1 (few (unit, head) pairs, many tokens: the Burgers U-Net has 16 x 4 of them over 4096 tokens -- 64 blocks on 256 CUs): the
-  // token range is cut into `chunks` pieces, one block each, partial sums go to part[block][32][32] and linattn_ctx_merge_kernel adds them
-  __shared__ float red[4][DH][KST];
-  const int HD = heads * DH, RW = 3 * HD;
-  const int uh = blockIdx.x / chunks, chunk = blockIdx.x - uh * chunks;
-  const int unit = uh / heads, h = uh - unit * heads;
-  const int clen = ((n + chunks - 1) / chunks + 7) & ~7;
-  const int t0 = chunk * clen, t1 = min(n, t0 + clen);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, dd = lane & 31, hh = lane >> 5;
-  float km = 0.f, kinvl = 1.f;
-  if (MODE == 0) {
-    km = kstats[((int64_t)unit * HD + h * DH + dd) * 2 + 0];
-    kinvl = 1.0f / kstats[((int64_t)unit * HD + h * DH + dd) * 2 + 1];
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-  const float* base = qkv + ((int64_t)unit * n) * RW + h * DH + dd;
-  const float* ob = MODE == 1 ? other + ((int64_t)unit * n) * HD + h * DH + dd : nullptr;
-  // eight token pairs per round: all sixteen row loads of a round are requested before the first is used (one pair per
-  // iteration leaves a single 256-byte request in flight per wave and the kernel at ~1.5 TB/s)
-  constexpr int UN = 8;
-  for (int j0 = t0 + wave * 2; j0 < t1; j0 += 8 * UN) {
-    float ra[UN], rb[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const int j = j0 + 8 * u + hh;
-      const bool ok = j < t1;
-      if (MODE == 0) {
-        ra[u] = ok ? base[(int64_t)j * RW + HD] : 0.f;
-        rb[u] = ok ? base[(int64_t)j * RW + 2 * HD] : 0.f;
-      } else {
-        ra[u] = ok ? base[(int64_t)j * RW] : 0.f;
-        rb[u] = ok ? ob[(int64_t)j * HD] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const bool ok = j0 + 8 * u + hh < t1;
-      float a;
-      if (MODE == 0) {
-        a = ok ? expf(ra[u] - km) * kinvl : 0.f;
-      } else {
-        float mx = group_max<32>(ra[u]);
-        float ex = expf(ra[u] - mx);
-        float sm = group_sum<32>(ex);
-        a = ok ? scale * ex / sm : 0.f;
-      }
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, rb[u], acc, 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 16; ++e) red[wave][(e & 3) + 8 * (e >> 2) + 4 * hh][dd] = acc[e];
-  __syncthreads();
-  // 1024 outputs / 256 threads
-  if (chunks > 1) {
-    float* po = part + (int64_t)blockIdx.x * DH * DH;
-    for (int o = threadIdx.x; o < DH * DH; o += 256) {
-      int r = o >> 5, c = o & 31;
-      po[o] = (red[0][r][c] + red[1][r][c]) + (red[2][r][c] + red[3][r][c]);
-    }
-    return;
-  }
-  float* co = ctx_out + ((int64_t)unit * heads + h) * DH * DH;
-  const float* ci = MODE == 1 ? ctx_in + ((int64_t)unit * heads + h) * DH * DH : nullptr;
-  for (int o = threadIdx.x; o < DH * DH; o += 256) {
-    int r = o >> 5, c = o & 31;
-    float v = (red[0][r][c] + red[1][r][c]) + (red[2][r][c] + red[3][r][c]);
-    co[o] = v;
-    if (MODE == 1) red[0][r][c] = v * ci[o];   // each (r,c) is owned by exactly one thread
-  }
-  if (MODE == 1) {
-    __syncthreads();
-    if (threadIdx.x < DH) {
-      float t = 0.f;
-      for (int c = 0; c < DH; ++c) t += red[0][threadIdx.x][c];
-      tvec[((int64_t)unit * heads + h) * DH + threadIdx.x] = t;
-    }
-  }
-}
-
-// sum of the chunk partials of linattn_ctx_kernel in chunk order; MODE 1 also T[d] = sum_e dctx[d][e] ctx[d][e]
-template <int MODE>
-__global__ __launch_bounds__(256) void linattn_ctx_merge_kernel(const float* __restrict__ part, const float* __restrict__ ctx_in,
-                                                                 float* __restrict__ ctx_out, float* __restrict__ tvec, int chunks) {
-  __shared__ float red[DH][KST];
-  const int64_t uh = blockIdx.x;
-  const float* p0 = part + uh * chunks * DH * DH;
-  float* co = ctx_out + uh * DH * DH;
-  const float* ci = MODE == 1 ? ctx_in + uh * DH * DH : nullptr;
-  for (int o = threadIdx.x; o < DH * DH; o += 256) {
-    float v = 0.f;
-    for (int c = 0; c < chunks; ++c) v += p0[c * DH * DH + o];
-    co[o] = v;
-    if (MODE == 1) red[o >> 5][o & 31] = v * ci[o];
-  }
-  if (MODE == 1) {
-    __syncthreads();
-    if (threadIdx.x < DH) {
-      float t = 0.f;
-      for (int c = 0; c < DH; ++c) t += red[threadIdx.x][c];
-      tvec[uh * DH + threadIdx.x] = t;
-    }
-  }
-}
-// pieces of the token range per (unit, head): enough blocks for ~2 per CU, at least 128 tokens each, at most LA_MAXCHUNKS
-#define LA_MAXCHUNKS 16
-static int la_ctx_chunks(int64_t units, int heads, int n_tok) {
-  const int64_t uh = units * heads;
-  int64_t c = (2 * (int64_t)wdno_num_cus() + uh - 1) / uh;
-  if (c > n_tok / 128) c = n_tok / 128;
-  if (c > LA_MAXCHUNKS) c = LA_MAXCHUNKS;
-  if (c < 1) c = 1;
-  return (int)c;
-}
-template <int MODE>
-static void la_ctx_launch(const float* qkv, const float* other, const float* kstats, const float* ctx_in, float* ctx_out, float* tvec, float* part,
-                          int64_t units, int n_tok, int heads, float scale, int chunks, hipStream_t st) {
-  if (!part) chunks = 1;
-  linattn_ctx_kernel<MODE><<<(unsigned)(units * heads * chunks), 256, 0, st>>>(qkv, other, kstats, ctx_in, ctx_out, tvec, n_tok, heads, scale, chunks, part);
-  if (chunks > 1) linattn_ctx_merge_kernel<MODE><<<(unsigned)(units * heads), 256, 0, st>>>(part, ctx_in, ctx_out, tvec, chunks);
-}
-
-// pass 3: out[n][e] = scale * sum_d ctx[d][e] * softmax_d(q[n])[d]; one thread per (token, head)
-__global__ __launch_bounds__(256) void linattn_out_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx, float* __restrict__ out,
-                                   int n, int heads, float scale, float* __restrict__ amax_rec) {
-  extern __shared__ __attribute__((aligned(16))) float cs[];   // [heads][32][32]
-  const int HD = heads * DH, RW = 3 * HD;
-  const int unit = blockIdx.x;
-  const int h = threadIdx.x >> 6;
-  for (int e = threadIdx.x; e < heads * DH * DH; e += blockDim.x) cs[e] = ctx[(int64_t)unit * heads * DH * DH + e];
-  __syncthreads();
-  const int jt = blockIdx.y * 64 + (threadIdx.x & 63);
-  const bool ok = jt < n;
-  const int j = ok ? jt : n - 1;           // lanes past the last token redo it (all lanes stay active for the amax reduction) and store nothing
-  const float4* qp = reinterpret_cast<const float4*>(qkv + ((int64_t)unit * n + j) * RW + h * DH);
-  float q[DH];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { float4 v = qp[e]; q[4 * e] = v.x; q[4 * e + 1] = v.y; q[4 * e + 2] = v.z; q[4 * e + 3] = v.w; }
-  float mx = q[0];
-#pragma unroll
-  for (int e = 1; e < DH; ++e) mx = fmaxf(mx, q[e]);
-  float sm = 0.f;
-#pragma unroll
-  for (int e = 0; e < DH; ++e) { q[e] = expf(q[e] - mx); sm += q[e]; }
-  float f = scale / sm;
-  float o[DH];
-#pragma unroll
-  for (int e = 0; e < DH; ++e) o[e] = 0.f;
-  const float4* cp = reinterpret_cast<const float4*>(cs + h * DH * DH);
-#pragma unroll
-  for (int d = 0; d < DH; ++d) {
-    float w = q[d] * f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float4 c = cp[d * 8 + e];
-      o[4 * e] = fmaf(w, c.x, o[4 * e]); o[4 * e + 1] = fmaf(w, c.y, o[4 * e + 1]);
-      o[4 * e + 2] = fmaf(w, c.z, o[4 * e + 2]); o[4 * e + 3] = fmaf(w, c.w, o[4 * e + 3]);
-    }
-  }
-  float4* op = reinterpret_cast<float4*>(out + ((int64_t)unit * n + j) * HD + h * DH);
-  float am = 0.f;
-  if (ok) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) op[e] = make_float4(o[4 * e], o[4 * e + 1], o[4 * e + 2], o[4 * e + 3]);
-  }
-#pragma unroll
-  for (int e = 0; e < DH; ++e) am = fmaxf(am, fabsf(o[e]));
-  if (amax_rec) wave_amax_emit(am, amax_rec, (int)((blockIdx.y * gridDim.x + blockIdx.x) * heads + h));
-}
-
-// backward pass B2: one thread per (token, head):
-//   dq = scale * qsm * (dqs - <qsm, dqs>),  dqs[d] = sum_e dout[e] ctx[d][e]
-//   dv[e] = sum_d ks[d] dctx[d][e] ; dk[d] = ks[d] * (sum_e v[e] dctx[d][e] - T[d])
-__global__ __launch_bounds__(256) void linattn_bwd_tok_kernel(const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ kstats,
-                                       const float* __restrict__ ctx, const float* __restrict__ dctx, const float* __restrict__ tvec,
-                                       float* __restrict__ dqkv, int n, int heads, float scale, float* __restrict__ amax_rec) {
-  extern __shared__ __attribute__((aligned(16))) float sm_[];
-  const int HD = heads * DH, RW = 3 * HD;
-  float* cs = sm_;                       // [heads][32][32]
-  float* ds = cs + heads * DH * DH;      // [heads][32][32]
-  float* km = ds + heads * DH * DH;      // [heads*32]
-  float* kl = km + HD;                   // 1/l
-  float* tv = kl + HD;
-  const int unit = blockIdx.x;
-  const int h = threadIdx.x >> 6;
-  for (int e = threadIdx.x; e < heads * DH * DH; e += blockDim.x) {
-    cs[e] = ctx[(int64_t)unit * heads * DH * DH + e];
-    ds[e] = dctx[(int64_t)unit * heads * DH * DH + e];
-  }
-  for (int e = threadIdx.x; e < HD; e += blockDim.x) {
-    km[e] = kstats[((int64_t)unit * HD + e) * 2];
-    kl[e] = 1.0f / kstats[((int64_t)unit * HD + e) * 2 + 1];
-    tv[e] = tvec[(int64_t)unit * HD + e];
-  }
-  __shared__ unsigned blk_amax;
-  if (threadIdx.x == 0) blk_amax = 0u;
-  __syncthreads();
-  const int j = blockIdx.y * 64 + (threadIdx.x & 63);
-  if (j >= n) return;                       // (a finished wave no longer counts at the barrier below)
-  float am = 0.f;
-  const int64_t row = (int64_t)unit * n + j;
-  const float4* cp = reinterpret_cast<const float4*>(cs + h * DH * DH);
-  const float4* dp = reinterpret_cast<const float4*>(ds + h * DH * DH);
-  float* wq = dqkv + row * RW + h * DH;
-  {  // ---- dq
-    float q[DH], go[DH];
-    const float4* qp = reinterpret_cast<const float4*>(qkv + row * RW + h * DH);
-    const float4* gp = reinterpret_cast<const float4*>(dout + row * HD + h * DH);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float4 v = qp[e]; q[4 * e] = v.x; q[4 * e + 1] = v.y; q[4 * e + 2] = v.z; q[4 * e + 3] = v.w;
-      float4 g = gp[e]; go[4 * e] = g.x; go[4 * e + 1] = g.y; go[4 * e + 2] = g.z; go[4 * e + 3] = g.w;
-    }
-    float mx = q[0];
-#pragma unroll
-    for (int e = 1; e < DH; ++e) mx = fmaxf(mx, q[e]);
-    float sm = 0.f;
-#pragma unroll
-    for (int e = 0; e < DH; ++e) { q[e] = expf(q[e] - mx); sm += q[e]; }
-    float inv = 1.0f / sm, dot = 0.f;
-    float dqs[DH];
-#pragma unroll
-    for (int d = 0; d < DH; ++d) {
-      float a = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float4 c = cp[d * 8 + e];
-        a = fmaf(go[4 * e], c.x, a); a = fmaf(go[4 * e + 1], c.y, a); a = fmaf(go[4 * e + 2], c.z, a); a = fmaf(go[4 * e + 3], c.w, a);
-      }
-      q[d] *= inv;
-      dqs[d] = a;
-      dot = fmaf(q[d], a, dot);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float4 v = make_float4(scale * q[4 * e] * (dqs[4 * e] - dot), scale * q[4 * e + 1] * (dqs[4 * e + 1] - dot),
-                                   scale * q[4 * e + 2] * (dqs[4 * e + 2] - dot), scale * q[4 * e + 3] * (dqs[4 * e + 3] - dot));
-      reinterpret_cast<float4*>(wq)[e] = v;
-      am = amax4(am, v);
-    }
-  }
-  {  // ---- dk, dv
-    float ks[DH], vv[DH], dv[DH];
-    const float4* kp = reinterpret_cast<const float4*>(qkv + row * RW + HD + h * DH);
-    const float4* vp = reinterpret_cast<const float4*>(qkv + row * RW + 2 * HD + h * DH);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float4 v = kp[e]; ks[4 * e] = v.x; ks[4 * e + 1] = v.y; ks[4 * e + 2] = v.z; ks[4 * e + 3] = v.w;
-      float4 u = vp[e]; vv[4 * e] = u.x; vv[4 * e + 1] = u.y; vv[4 * e + 2] = u.z; vv[4 * e + 3] = u.w;
-    }
-#pragma unroll
-    for (int e = 0; e < DH; ++e) { ks[e] = expf(ks[e] - km[h * DH + e]) * kl[h * DH + e]; dv[e] = 0.f; }
-    float dk[DH];
-#pragma unroll
-    for (int d = 0; d < DH; ++d) {
-      float a = 0.f, w = ks[d];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float4 c = dp[d * 8 + e];
-        a = fmaf(vv[4 * e], c.x, a); a = fmaf(vv[4 * e + 1], c.y, a); a = fmaf(vv[4 * e + 2], c.z, a); a = fmaf(vv[4 * e + 3], c.w, a);
-        dv[4 * e] = fmaf(w, c.x, dv[4 * e]); dv[4 * e + 1] = fmaf(w, c.y, dv[4 * e + 1]);
-        dv[4 * e + 2] = fmaf(w, c.z, dv[4 * e + 2]); dv[4 * e + 3] = fmaf(w, c.w, dv[4 * e + 3]);
-      }
-      dk[d] = w * (a - tv[h * DH + d]);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float4 gk = make_float4(dk[4 * e], dk[4 * e + 1], dk[4 * e + 2], dk[4 * e + 3]);
-      const float4 gv = make_float4(dv[4 * e], dv[4 * e + 1], dv[4 * e + 2], dv[4 * e + 3]);
-      reinterpret_cast<float4*>(wq + HD)[e] = gk;
-      reinterpret_cast<float4*>(wq + 2 * HD)[e] = gv;
-      am = amax4(amax4(am, gk), gv);
-    }
-  }
-  if (amax_rec) {     // lanes past the last token have left: an LDS atomic per lane instead of a wave shuffle, one global atomic per block
-    atomicMax(&blk_amax, __float_as_uint(am));
-    __syncthreads();
-    if (threadIdx.x == 0)
-      atomicMax(reinterpret_cast<unsigned*>(amax_rec) + ((blockIdx.y * gridDim.x + blockIdx.x) & (WDNO_AMAX_SLOTS - 1)) * WDNO_AMAX_STRIDE, blk_amax);
-  }
-}
-
-// The same backward pass on MFMA tiles: one wave per (unit, head, 32-token chunk), the four waves of a block take four
-// consecutive chunks of one (unit, head) and share its ctx / dctx tiles. The thread-per-token kernel above needs 256 + 182
-// registers (one wave per SIMD) and every lane walks its own 1.5-KB-strided rows; here the rows are staged through LDS by
-// coalesced 128-byte reads (am_stage_rows) and the three 32 x 32 x 32 products run on v_mfma_f32_32x32x2_f32, computed
-// TRANSPOSED so that lane (token, half) ends up with 16 of the token's 32 channels (runs of four: 16-byte stores):
-//   dqs^T[d][t] = sum_e ctx[d][e]  dout[t][e]       a^T[d][t] = sum_e dctx[d][e] v[t][e]       dv^T[e][t] = sum_d dctx[d][e] ks[t][d]
-// The channel softmax of q and the <qsm, dqs> dot product need the other half of the row: one lane ^ 32 exchange each.
-#define LAM_TILE (32 * AM_TS)
-__global__ __launch_bounds__(256, 2) void linattn_bwd_tok_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
-                                                                       const float* __restrict__ kstats, const float* __restrict__ ctx,
-                                                                       const float* __restrict__ dctx, const float* __restrict__ tvec,
-                                                                       float* __restrict__ dqkv, int n, int heads, float scale,
-                                                                       float* __restrict__ amax_rec, _Float16* __restrict__ pl_hi = nullptr,
-                                                                       _Float16* __restrict__ pl_lo = nullptr, const float* __restrict__ rec_qkv = nullptr,
-                                                                       const float* __restrict__ rec_dout = nullptr,
-                                                                       const float* __restrict__ rec_dctx = nullptr, float* __restrict__ pl_scale = nullptr) {
-  extern __shared__ __attribute__((aligned(16))) float lsm[];
-  float* Tc = lsm;                       // ctx  [d][e]
-  float* Td = Tc + LAM_TILE;             // dctx [d][e]
-  float* km = Td + LAM_TILE;             // per d: max, 1 / sum of the token softmax of k; T[d]
-  float* kl = km + DH;
-  float* tv = kl + DH;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, hh = lane >> 5;
-  float* T1 = tv + DH + wave * 3 * LAM_TILE;      // q, then dout
-  float* T2 = T1 + LAM_TILE;                      // k
-  float* T3 = T2 + LAM_TILE;                      // v
-  const int HD = heads * DH, RW = 3 * HD;
-  const int unit = blockIdx.x / heads, h = blockIdx.x - unit * heads;
-  {
-    const float* cs = ctx + ((int64_t)unit * heads + h) * DH * DH;
-    const float* ds = dctx + ((int64_t)unit * heads + h) * DH * DH;
-    for (int e = threadIdx.x; e < DH * DH / 4; e += 256) {
-      const int r = e >> 3, c4 = (e & 7) * 4;
-      *reinterpret_cast<float4*>(Tc + r * AM_TS + c4) = reinterpret_cast<const float4*>(cs)[e];
-      *reinterpret_cast<float4*>(Td + r * AM_TS + c4) = reinterpret_cast<const float4*>(ds)[e];
-    }
-    if (threadIdx.x < DH) {
-      const int64_t col = (int64_t)unit * HD + h * DH + threadIdx.x;
-      km[threadIdx.x] = kstats[col * 2];
-      kl[threadIdx.x] = 1.0f / kstats[col * 2 + 1];
-      tv[threadIdx.x] = tvec[col];
-    }
-  }
-  __syncthreads();
-  float am = 0.f;
-  // Planes output (wdno_linattn_bwd_planes): with A = max|qkv|, G = max|dout|, D = max|dctx| (measured), ks, qsm <= 1 and |ctx| <= A:
-  // |dq| <= 2 scale 32 A G,  |dk| <= 2 * 32 A D,  |dv| <= 32 D.
-  float ps = 1.0f;
-  if (pl_hi && pl_lo) {
-    const float A = amax_record_read(rec_qkv), G = amax_record_read(rec_dout), D = amax_record_read(rec_dctx);
-    ps = scale_from_amax(1.01f * fmaxf(64.f * scale * A * G, fmaxf(64.f * A * D, 32.f * D)));
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) pl_scale[0] = ps;
-  }
-  const int t0 = (blockIdx.y * 4 + wave) * 32;
-  if (t0 < n) {                                     // (no block-wide barrier below)
-    const int nv = min(32, n - t0);
-    const bool tok = li < nv;
-    const int64_t row0 = (int64_t)unit * n + t0;
-    const float* qb = am_uniform(qkv + row0 * RW + h * DH);
-    const float* gb = am_uniform(dout + row0 * HD + h * DH);
-    float* db = const_cast<float*>(am_uniform(dqkv + row0 * RW + h * DH)) + (unsigned)(tok ? li : 0) * (unsigned)RW;
-    const int64_t pbase = row0 * RW + h * DH + (int64_t)((unsigned)(tok ? li : 0) * (unsigned)RW);
-    am_stage_rows(T1, qb, (unsigned)RW, nullptr, nullptr, 1.0f, nv, lane);
-    am_stage_rows(T2, qb + HD, (unsigned)RW, nullptr, nullptr, 1.0f, nv, lane);
-    am_stage_rows(T3, qb + 2 * HD, (unsigned)RW, nullptr, nullptr, 1.0f, nv, lane);
-    __builtin_amdgcn_wave_barrier();
-    // channel softmax of this lane's token: channels d = 8*e4 + 4*hh + c here, the other sixteen in lane ^ 32
-    float qsm[16];
-    {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int e4 = 0; e4 < 4; ++e4) {
-        const float4 t = *reinterpret_cast<const float4*>(T1 + li * AM_TS + 8 * e4 + 4 * hh);
-        qsm[4 * e4] = t.x; qsm[4 * e4 + 1] = t.y; qsm[4 * e4 + 2] = t.z; qsm[4 * e4 + 3] = t.w;
-        mx = fmaxf(fmaxf(mx, fmaxf(t.x, t.y)), fmaxf(t.z, t.w));
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      float sm = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { qsm[e] = expf(qsm[e] - mx); sm += qsm[e]; }
-      sm += __shfl_xor(sm, 32);
-      const float inv = 1.0f / sm;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) qsm[e] *= inv;
-    }
-    __builtin_amdgcn_wave_barrier();                // every lane has read its q row: the tile takes dout now
-    am_stage_rows(T1, gb, (unsigned)HD, nullptr, nullptr, 1.0f, nv, lane);
-    __builtin_amdgcn_wave_barrier();
-    {   // ---- dq = scale * qsm * (dqs - <qsm, dqs>)
-      float ca[16], ga[16];
-      am_sel(Tc, li, hh, ca);
-      am_sel(T1, li, hh, ga);
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[m], ga[m], acc, 0, 0, 0);
-      float dot = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) dot = fmaf(qsm[e], acc[e], dot);
-      dot += __shfl_xor(dot, 32);
-      float4 vv[4];
-#pragma unroll
-      for (int e4 = 0; e4 < 4; ++e4) {
-        const float4 v = make_float4(scale * qsm[4 * e4] * (acc[4 * e4] - dot), scale * qsm[4 * e4 + 1] * (acc[4 * e4 + 1] - dot),
-                                     scale * qsm[4 * e4 + 2] * (acc[4 * e4 + 2] - dot), scale * qsm[4 * e4 + 3] * (acc[4 * e4 + 3] - dot));
-        vv[e4] = v;
-        if (tok && !pl_hi) *reinterpret_cast<float4*>(db + 8 * e4 + 4 * hh) = v;
-        if (tok) am = amax4(am, v);                      // lanes past the last token hold values of no token
-      }
-      if (tok && pl_hi) am_store_row_planes(pl_hi, pl_lo, pbase, hh, vv, ps);
-    }
-    {   // ---- dk[d] = ks[d] * (sum_e v[e] dctx[d][e] - T[d]),  ks = exp(k - max) / sum
-      float da[16], va[16];
-      am_sel(Td, li, hh, da);
-      am_sel(T3, li, hh, va);
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(da[m], va[m], acc, 0, 0, 0);
-      float4 vk[4];
-#pragma unroll
-      for (int e4 = 0; e4 < 4; ++e4) {
-        const int d0 = 8 * e4 + 4 * hh;
-        const float4 kk = *reinterpret_cast<const float4*>(T2 + li * AM_TS + d0);
-        const float4 m4 = *reinterpret_cast<const float4*>(km + d0), l4 = *reinterpret_cast<const float4*>(kl + d0);
-        const float4 t4 = *reinterpret_cast<const float4*>(tv + d0);
-        const float4 v = make_float4(expf(kk.x - m4.x) * l4.x * (acc[4 * e4] - t4.x), expf(kk.y - m4.y) * l4.y * (acc[4 * e4 + 1] - t4.y),
-                                     expf(kk.z - m4.z) * l4.z * (acc[4 * e4 + 2] - t4.z), expf(kk.w - m4.w) * l4.w * (acc[4 * e4 + 3] - t4.w));
-        vk[e4] = v;
-        if (tok && !pl_hi) *reinterpret_cast<float4*>(db + HD + d0) = v;
-        if (tok) am = amax4(am, v);
-      }
-      if (tok && pl_hi) am_store_row_planes(pl_hi, pl_lo, pbase + HD, hh, vk, ps);
-    }
-    {   // ---- dv[e] = sum_d ks[d] dctx[d][e]: row operand = dctx read by columns (lane = e), column operand = ks[t][2m + hh]
-      float da[16], ka[16];
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const int d = AM_D(m, hh);
-        da[m] = Td[d * AM_TS + li];
-        ka[m] = expf(T2[li * AM_TS + d] - km[d]) * kl[d];
-      }
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(da[m], ka[m], acc, 0, 0, 0);
-      float4 vd[4];
-#pragma unroll
-      for (int e4 = 0; e4 < 4; ++e4) {
-        const float4 v = make_float4(acc[4 * e4], acc[4 * e4 + 1], acc[4 * e4 + 2], acc[4 * e4 + 3]);
-        vd[e4] = v;
-        if (tok && !pl_hi) *reinterpret_cast<float4*>(db + 2 * HD + 8 * e4 + 4 * hh) = v;
-        if (tok) am = amax4(am, v);
-      }
-      if (tok && pl_hi) am_store_row_planes(pl_hi, pl_lo, pbase + 2 * HD, hh, vd, ps);
-    }
-  }
-  if (amax_rec) wave_amax_emit(am, amax_rec, (int)((blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave));
-}
-
-// pass 3 on MFMA tiles (same layout as linattn_bwd_tok_mfma_kernel): out^T[e][t] = sum_d ctx[d][e] qs[t][d], qs = scale * softmax_d(q).
-// Row operand = ctx read by columns (lane = e), column operand = qs[t][2m + hh]; the two halves of a token's softmax sit in
-// lanes t and t + 32.
-__global__ __launch_bounds__(256, 2) void linattn_out_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
-                                                                   float* __restrict__ out, int n, int heads, float scale,
-                                                                   float* __restrict__ amax_rec, _Float16* __restrict__ pl_hi = nullptr,
-                                                                   _Float16* __restrict__ pl_lo = nullptr, const float* __restrict__ rec_qkv = nullptr,
-                                                                   float* __restrict__ pl_scale = nullptr) {
-  __shared__ __attribute__((aligned(16))) float Tc[LAM_TILE];
-  __shared__ __attribute__((aligned(16))) float Tq[4][LAM_TILE];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, hh = lane >> 5;
-  const int HD = heads * DH, RW = 3 * HD;
-  const int unit = blockIdx.x / heads, h = blockIdx.x - unit * heads;
-  {
-    const float* cs = ctx + ((int64_t)unit * heads + h) * DH * DH;
-    for (int e = threadIdx.x; e < DH * DH / 4; e += 256) {
-      const int r = e >> 3, c4 = (e & 7) * 4;
-      *reinterpret_cast<float4*>(Tc + r * AM_TS + c4) = reinterpret_cast<const float4*>(cs)[e];
-    }
-  }
-  __syncthreads();
-  float ops = 1.0f;
-  if (pl_hi && pl_lo) {
-    ops = scale_from_amax(1.01f * scale * amax_record_read(rec_qkv));
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) pl_scale[0] = ops;
-  }
-  float am = 0.f;
-  const int t0 = (blockIdx.y * 4 + wave) * 32;
-  if (t0 < n) {
-    const int nv = min(32, n - t0);
-    const bool tok = li < nv;
-    const int64_t row0 = (int64_t)unit * n + t0;
-    float* T1 = Tq[wave];
-    am_stage_rows(T1, am_uniform(qkv + row0 * RW + h * DH), (unsigned)RW, nullptr, nullptr, 1.0f, nv, lane);
-    __builtin_amdgcn_wave_barrier();
-    float qs[16], ca[16];
-    am_sel(T1, li, hh, qs);
-    float mx = qs[0];
-#pragma unroll
-    for (int m = 1; m < 16; ++m) mx = fmaxf(mx, qs[m]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    float sm = 0.f;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) { qs[m] = expf(qs[m] - mx); sm += qs[m]; }
-    sm += __shfl_xor(sm, 32);
-    const float f = scale / sm;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) { qs[m] *= f; ca[m] = Tc[AM_D(m, hh) * AM_TS + li]; }
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[m], qs[m], acc, 0, 0, 0);
-    float* orow = out + (row0 + (tok ? li : 0)) * HD + h * DH;
-    float4 vo[4];
-#pragma unroll
-    for (int e4 = 0; e4 < 4; ++e4) {
-      const float4 v = make_float4(acc[4 * e4], acc[4 * e4 + 1], acc[4 * e4 + 2], acc[4 * e4 + 3]);
-      vo[e4] = v;
-      if (tok && !pl_hi) *reinterpret_cast<float4*>(orow + 8 * e4 + 4 * hh) = v;
-      am = amax4(am, v);
-    }
-    // planes for the to_out projection INSTEAD of the fp32 tensor (the backward works from ctx, not from out):
-    // qs sums to `scale` over d and |ctx| <= max|v|, so |out| <= scale * max|qkv|
-    if (tok && pl_hi) am_store_row_planes(pl_hi, pl_lo, (row0 + li) * HD + h * DH, hh, vo, ops);
-  }
-  if (amax_rec) wave_amax_emit(am, amax_rec, (int)((blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave));
-}
-
-static int la_check(int64_t units, int n, int heads) {
-  if (units <= 0 || n <= 0 || heads <= 0 || units > 0x7fffffff / 8) return WDNO_EINVAL;
-  if (heads != 1 && heads != 2 && heads != 4) return WDNO_EUNSUPPORTED;   // 64*heads threads per block
-  return WDNO_OK;
-}
-// backward workspace: dctx [units,heads,32,32] + T [units,heads,32]
-extern "C" size_t wdno_linattn_ws_bytes(int64_t units, int heads) {
-  const size_t chunk_part = units * heads <= 2 * (int64_t)wdno_num_cus() ? (size_t)units * heads * LA_MAXCHUNKS * DH * DH : 0;      // partial contexts of a chunked token range
-  return ((size_t)units * heads * DH * DH + (size_t)units * heads * DH + chunk_part) * sizeof(float);
-}
-// the cuts of a call: the ONE place that decides them (the launch paths below and wdno_linattn_plan both ask here)
-static int la_choose(int64_t units, int n_tok, int heads, bool backward, size_t ws_bytes, wdno_la_plan& pl) {
-  pl = wdno_la_plan{0, 0, 0, 0, la_check(units, n_tok, heads)};
-  if (pl.rc) return pl.rc;
-  if (backward && ws_bytes < wdno_linattn_ws_bytes(units, heads)) return pl.rc = WDNO_EWORKSPACE;
-  if (!backward) {
-    pl.kstats_chunks = n_tok / 64;
-    pl.kstats_chunks = pl.kstats_chunks < 1 ? 1 : (pl.kstats_chunks > 16 ? 16 : pl.kstats_chunks);
-  }
-  // forward: the chunk partials always have room (they go through `out` / the hi plane); backward: the workspace has the room only up to 2 x CUs (unit, head) pairs
-  pl.ctx_chunks = !backward || units * heads <= 2 * (int64_t)wdno_num_cus() ? la_ctx_chunks(units, heads, n_tok) : 1;
-  pl.family = wdno_debug_mode == WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV ? 1 : 0;
-  pl.token_tiles = cdiv(n_tok, pl.family ? 64 : 128);
-  return WDNO_OK;
-}
-extern "C" int wdno_linattn_plan(int64_t units, int n_tok, int heads, int backward, size_t ws_bytes, wdno_la_plan* out) {
-  if (!out) return WDNO_EINVAL;
-  la_choose(units, n_tok, heads, backward != 0, ws_bytes, *out);
-  return WDNO_OK;
-}
-extern "C" int wdno_linattn_fwd(const float* qkv, float* out, float* kstats, float* ctx, int64_t units, int n_tok, int heads,
-                                float scale, wdno_stream_t s) {
-  return wdno_linattn_fwd_amax(qkv, out, kstats, ctx, nullptr, units, n_tok, heads, scale, s);
-}
-extern "C" int wdno_linattn_fwd_amax(const float* qkv, float* out, float* kstats, float* ctx, float* amax_rec, int64_t units, int n_tok,
-                                     int heads, float scale, wdno_stream_t s) {
-  wdno_la_plan pl;
-  int rc = la_choose(units, n_tok, heads, false, 0, pl);
-  if (rc) return rc;
-  hipStream_t st = as_stream(s);
-  // partial statistics go through `ctx` (written only afterwards by the context kernel): chunks * HD * 2 <= 32 * HD floats per unit
-  const int chunks = pl.kstats_chunks;
-  if (chunks == 1) {
-    linattn_kstats_kernel<<<(unsigned)units, 256, 0, st>>>(qkv, kstats, n_tok, heads * DH, 1);
-  } else {
-    linattn_kstats_kernel<<<(unsigned)(units * chunks), 256, 0, st>>>(qkv, ctx, n_tok, heads * DH, chunks);
-    const int64_t cols = units * heads * DH;
-    linattn_kstats_merge_kernel<<<(unsigned)cdiv64(cols, 256), 256, 0, st>>>(ctx, kstats, cols, heads * DH, chunks);
-  }
-  // (chunk partials of the context go through `out`, which only the output kernel below writes: units * heads * chunks * 1024 floats
-  // <= units * n_tok * HD because chunks <= n_tok / 128)
-  la_ctx_launch<0>(qkv, nullptr, kstats, nullptr, ctx, nullptr, out, units, n_tok, heads, scale, pl.ctx_chunks, st);
-  if (pl.family == 0) {            // else: the thread-per-token kernel
-    linattn_out_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)pl.token_tiles), 256, 0, st>>>(qkv, ctx, out, n_tok, heads, scale, amax_rec);
-    return wdno_check_launch();
-  }
-  size_t lds = (size_t)heads * DH * DH * sizeof(float);
-  linattn_out_kernel<<<dim3((unsigned)units, (unsigned)pl.token_tiles), 64 * heads, lds, st>>>(qkv, ctx, out, n_tok, heads, scale, amax_rec);
-  return wdno_check_launch();
-}
-extern "C" int wdno_linattn_bwd(const float* qkv, const float* dout, const float* kstats, const float* ctx, float* dqkv,
-                                void* ws, size_t ws_bytes, int64_t units, int n_tok, int heads, float scale, wdno_stream_t s) {
-  return wdno_linattn_bwd_amax(qkv, dout, kstats, ctx, dqkv, nullptr, ws, ws_bytes, units, n_tok, heads, scale, s);
-}
-extern "C" int wdno_linattn_bwd_amax(const float* qkv, const float* dout, const float* kstats, const float* ctx, float* dqkv,
-                                     float* amax_rec, void* ws, size_t ws_bytes, int64_t units, int n_tok, int heads, float scale,
-                                     wdno_stream_t s) {
-  wdno_la_plan pl;
-  int rc = la_choose(units, n_tok, heads, true, ws_bytes, pl);
-  if (rc) return rc;
-  hipStream_t st = as_stream(s);
-  float* dctx = (float*)ws;
-  float* tvec = dctx + (size_t)units * heads * DH * DH;
-  float* cpart = units * heads <= 2 * (int64_t)wdno_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
-  la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, pl.ctx_chunks, st);
-  if (pl.family == 0) {            // else: the thread-per-token kernel
-    const size_t lds2 = ((size_t)(2 + 4 * 3) * LAM_TILE + 3 * DH) * sizeof(float);
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)linattn_bwd_tok_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); attr_done = true; }
-    linattn_bwd_tok_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)pl.token_tiles), 256, lds2, st>>>(qkv, dout, kstats, ctx, dctx, tvec,
-                                                                                                          dqkv, n_tok, heads, scale, amax_rec);
-    return wdno_check_launch();
-  }
-  size_t lds = ((size_t)2 * heads * DH * DH + 3 * heads * DH) * sizeof(float);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)linattn_bwd_tok_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  linattn_bwd_tok_kernel<<<dim3((unsigned)units, (unsigned)pl.token_tiles), 64 * heads, lds, st>>>(qkv, dout, kstats, ctx, dctx, tvec, dqkv,
-                                                                                                n_tok, heads, scale, amax_rec);
-  return wdno_check_launch();
-}
-
-// dqkv as fp16 planes for the gradient kernels of the qkv projection (MFMA token kernel only). rec_dctx: a zeroed amax record, receives
-// max|dctx| (a sweep over the small dctx tensor between the two launches).
-extern "C" int wdno_linattn_bwd_planes(const float* qkv, const float* dout, const float* kstats, const float* ctx, void* dqkv_hi,
-                                       void* dqkv_lo, float* dqkv_scale, const float* rec_qkv, const float* rec_dout, float* rec_dctx,
-                                       void* ws, size_t ws_bytes, int64_t units, int n_tok, int heads, float scale, wdno_stream_t s) {
-  int rc = la_check(units, n_tok, heads);
-  if (rc) return rc;
-  if (!dqkv_hi || (dqkv_lo && (!dqkv_scale || !rec_qkv || !rec_dout || !rec_dctx))) return WDNO_EINVAL;      // dqkv_lo == NULL: one bf16 plane
-  wdno_la_plan pl;
-  rc = la_choose(units, n_tok, heads, true, ws_bytes, pl);
-  if (rc) return rc;
-  hipStream_t st = as_stream(s);
-  float* dctx = (float*)ws;
-  float* tvec = dctx + (size_t)units * heads * DH * DH;
-  float* cpart = units * heads <= 2 * (int64_t)wdno_num_cus() ? tvec + (size_t)units * heads * DH : nullptr;
-  la_ctx_launch<1>(qkv, dout, nullptr, ctx, dctx, tvec, cpart, units, n_tok, heads, scale, pl.ctx_chunks, st);
-  if (dqkv_lo) {
-    rc = wdno_amax_record(dctx, (int64_t)units * heads * DH * DH, rec_dctx, s);
-    if (rc) return rc;
-  }
-  const size_t lds2 = ((size_t)(2 + 4 * 3) * LAM_TILE + 3 * DH) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)linattn_bwd_tok_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); attr_done = true; }
-  linattn_bwd_tok_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)cdiv(n_tok, 128)), 256, lds2, st>>>(
-      qkv, dout, kstats, ctx, dctx, tvec, nullptr, n_tok, heads, scale, nullptr, (_Float16*)dqkv_hi, (_Float16*)dqkv_lo, rec_qkv, rec_dout, rec_dctx,
-      dqkv_scale);
-  return wdno_check_launch();
-}
-
-// forward with out delivered as fp16 planes only (MFMA output kernel)
-extern "C" int wdno_linattn_fwd_planes(const float* qkv, void* out_hi, void* out_lo, float* out_scale, float* kstats, float* ctx,
-                                       const float* rec_qkv, int64_t units, int n_tok, int heads, float scale, wdno_stream_t s) {
-  int rc = la_check(units, n_tok, heads);
-  if (rc) return rc;
-  if (!out_hi || (out_lo && (!out_scale || !rec_qkv))) return WDNO_EINVAL;      // out_lo == NULL: one bf16 plane
-  wdno_la_plan pl;
-  la_choose(units, n_tok, heads, false, 0, pl);
-  hipStream_t st = as_stream(s);
-  const int chunks = pl.kstats_chunks;
-  if (chunks == 1) {
-    linattn_kstats_kernel<<<(unsigned)units, 256, 0, st>>>(qkv, kstats, n_tok, heads * DH, 1);
-  } else {
-    linattn_kstats_kernel<<<(unsigned)(units * chunks), 256, 0, st>>>(qkv, ctx, n_tok, heads * DH, chunks);
-    const int64_t cols = units * heads * DH;
-    linattn_kstats_merge_kernel<<<(unsigned)cdiv64(cols, 256), 256, 0, st>>>(ctx, kstats, cols, heads * DH, chunks);
-  }
-  // (chunk partials go through the hi plane: units * heads * chunks * 4096 bytes <= units * n_tok * HD * 2 because chunks <= n_tok / 128)
-  la_ctx_launch<0>(qkv, nullptr, kstats, nullptr, ctx, nullptr, (float*)out_hi, units, n_tok, heads, scale, pl.ctx_chunks, st);
-  linattn_out_mfma_kernel<<<dim3((unsigned)(units * heads), (unsigned)cdiv(n_tok, 128)), 256, 0, st>>>(
-      qkv, ctx, nullptr, n_tok, heads, scale, nullptr, (_Float16*)out_hi, (_Float16*)out_lo, rec_qkv, out_scale);
-  return wdno_check_launch();
+  return attn_bwd_run(qkv, rot_cos, rot_sin, bias, out, dout, nullptr, dbias, nullptr, d, scale, ws, ws_bytes, s, true, dqkv_hi, dqkv_lo,
+                      dqkv_scale, rec_qkv, rec_dout);
 }

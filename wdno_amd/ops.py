@@ -2263,7 +2263,7 @@ def attn_plan(direction, heads, n_uo, n_ui, n_tok, so=0, si=0, st=1, rot=False, 
 
 
 def linattn_plan(units, n_tok, heads, backward=False, ws_bytes=None):
-    """The cuts linear_attention makes (csrc/attention.hip): dict(kstats_chunks, ctx_chunks, token_tiles, family 'mfma' | 'tokens', rc).
+    """The cuts linear_attention makes (csrc/linattn.hip): dict(kstats_chunks, ctx_chunks, token_tiles, family 'mfma' | 'tokens', rc).
     ws_bytes None: the workspace the backward asks for. No launch, no device needed."""
     pl = _lib.LinAttnPlan()
     if ws_bytes is None:
