@@ -165,7 +165,7 @@ int wdno_split_f16_colsum(const float* x, const float* amax_rec, void* hi, void*
  * from the ConvTranspose3d weight w[C = in][K = out][1][4][4] itself; kd, kh, kw = 1, 2, 2.
  * modes 10 / 11: the forward operand of a 1 x 1 projection -- to_qkv [A = 384][B = C] / to_out [A = C][B = 128] of a temporal attention block with
  * 4 heads of 32 -- in the FRAGMENT ORDER wdno_tattn_fused_fwd reads at C = 128 / 256 (csrc/attn_fused_wide.hip streams its weights: the 64 lanes of
- * one matrix-operand load then read 1 KB of contiguous memory). Same bytes as mode 0, 16-byte groups permuted (csrc/conv_h3.hip: pack_split_body). */
+ * one matrix-operand load then read 1 KB of contiguous memory). Same bytes as mode 0, 16-byte groups permuted (csrc/conv_prep.hip: pack_split_body). */
 int wdno_pack_split_weight(const float* w, const float* amax, void* hi, void* lo, float* scale_out, int K, int C, int kd, int kh, int kw,
                            int A, int B, int mode, wdno_stream_t s);
 /* Multi-tensor forms of wdno_amax and wdno_pack_split_weight for the per-step refresh of all weights: one launch for any

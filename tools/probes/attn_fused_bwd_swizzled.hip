@@ -88,7 +88,7 @@ __device__ __forceinline__ int tb_woff(int f, int chunk) { return f * TF_C + ((c
 // halves offset of the 8-byte piece `piece` of row r in a plane tile
 __device__ __forceinline__ int tb_poff(int r, int piece) { return r * TB_PS + ((piece ^ ((r >> 1) & 7)) << 2); }
 // operand fragment from a [token][channel] image of 24 rows: lane (li, hh) receives channel ch0 + li of tokens 16 s + 8 hh + (0..7)
-// (conv_h3.hip: tr_frag; inside a 16-lane group lanes 4 j .. 4 j + 3 point at the four 8-byte pieces of row j). Tokens 24 .. 31 -- the
+// (conv_wgrad_h3.hip: tr_frag; inside a 16-lane group lanes 4 j .. 4 j + 3 point at the four 8-byte pieces of row j). Tokens 24 .. 31 -- the
 // upper lane half of step s = 1 -- come from the zero block.
 template <int S>
 __device__ __forceinline__ half8 tb_trf(const _Float16* img, int ch0, int lane, const _Float16* zb) {

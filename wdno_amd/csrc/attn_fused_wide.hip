@@ -7,7 +7,7 @@
 // four launches of 10-50 us that each wait for the one before. What differs from the 64-channel kernel: the head's 96 rows of W_qkv no longer
 // fit the register file (96 x C halves x 2 planes per wave), so the weight fragments are STREAMED from L2 per sequence, two k-step pairs per
 // trip: requested, waited for in full, consumed (attn_fused.h: why not overlapped). They are packed in FRAGMENT ORDER (pack modes 10 / 11 of
-// csrc/conv_h3.hip): the 64 lanes of one operand load read 1 KB of contiguous memory. Read from the row-major [384][C] operand the same
+// csrc/conv_prep.hip): the 64 lanes of one operand load read 1 KB of contiguous memory. Read from the row-major [384][C] operand the same
 // instruction touches 32 rows = 64 half-used cache lines, and the kernel is bound by the address / tag rate of the CU's one vector cache:
 // measured 132 -> 85 us at [8,24,20,20,128], 77 -> 46 us at [8,24,10,10,256], 42 -> 28 us at [8,24,10,10,128] (layer by layer: 153 / 74 /
 // 54 us). The contraction index may be permuted freely as long as both operands agree: k-step pair t of lane half hh covers channels
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void tattn_wide_fwd_kernel(TFusedP p) {
   const float inv_qkv = 1.0f / (ps * p.wq_scale[0]);
   const float sw_o = p.wo_scale[0];
   const int64_t fstride = (int64_t)p.HW * C;
-  // operands in fragment order (pack modes 10 / 11 of csrc/conv_h3.hip): [head][q|k|v][pair][step][lane][8] and [wave][tile][head][step][lane][8]
+  // operands in fragment order (pack modes 10 / 11 of csrc/conv_prep.hip): [head][q|k|v][pair][step][lane][8] and [wave][tile][head][step][lane][8]
   // (raw buffer loads: descriptor + one 32-bit lane offset + a uniform offset, see attn_fused.h)
   const unsigned wq_off = (unsigned)(h * 3 * NP * 2 * 64 + lane) * 16u;     // bytes; + ((ti NP + t) 2 + s) 1024
   const unsigned wo_off = (unsigned)(h * MT * 4 * 2 * 64 + lane) * 16u;     // + ((mt 4 + t) 2 + s) 1024

@@ -78,6 +78,8 @@ static inline int conv_persistent_grid(int64_t items) {
   if (items < grid) grid = (int)items;
   return grid;
 }
+// conv_prep.hip: the amax record (common.h) of x[n] by a sweep, for a forward launch whose epilogue could not fill it
+void conv_amax_record_launch(const float* x, int64_t n, float* rec, hipStream_t st);
 // conv.hip: the exact-fp32 forward kernel's tile for a geometry
 int wdno_conv_fwd_fp32_plan(const wdno_conv_geom* g, wdno_conv_plan* out);
 // conv_h3d.hip: LDS-DMA variant of the split-fp16 forward / data-gradient kernel. The chooser returns WDNO_EUNSUPPORTED for what these kernels
@@ -92,26 +94,6 @@ int wdno_conv_h3t_split(const wdno_conv_geom& g, int64_t P, int cus);
 int wdno_conv_fwd_h3_tap_choose(int shape, int tsplit, const ConvP& p, bool lp, ConvFwdChoice& c);
 int wdno_conv_fwd_h3_tap(const void* xh, const void* xl, const void* wh, const void* wl, const float* sx, const float* sw,
                          const float* bias, const float* residual, float* y, ConvP& p, const ConvFwdChoice& c, hipStream_t st);
-#ifdef __HIPCC__
-// s_waitcnt lgkmcnt(0) + s_barrier. The wait is the BUILTIN so that the compiler's own s_waitcnt bookkeeping sees it: behind an
-// asm-only wait it still counts the scalar loads of the previous tile's epilogue as possibly outstanding at the head of the
-// step loop, and (scalar loads return out of order) protects the first MFMA of every step with lgkmcnt(0) -- a wait for the
-// LDS reads issued just before it.
-// bf16 storage of two accumulator runs (channels 8 e + 4 hh .. + 3 and 8 (e + 1) + 4 hh .. + 3 of one pixel, the two lane halves hh = 0 / 1
-// holding the two halves of each group of eight): the halves trade runs (v_permlane32_swap), so that the lower half ends up with the eight
-// channels of group e and the upper half with those of group e + 1 -- ONE 16-byte store per lane instead of two 8-byte ones (with the
-// 8-byte stores the 256 x 128 single-plane kernel of the Burgers U-Net lost 2.7 %: 356 vs 366 us per launch).
-__device__ __forceinline__ uint4 bf16x8_from_runs(float4 va, float4 vb) {
-  const uint2 A = bf16x4_pack(va), B = bf16x4_pack(vb);
-  const auto sx = __builtin_amdgcn_permlane32_swap(A.x, B.x, false, false);
-  const auto sy = __builtin_amdgcn_permlane32_swap(A.y, B.y, false, false);
-  return make_uint4(sx[0], sy[0], sx[1], sy[1]);
-}
-__device__ __forceinline__ void lgkm0_barrier() {
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  asm volatile("s_barrier" : : : "memory");
-}
-#endif
 static inline void fill_params(ConvP& p, const wdno_conv_geom* g) {
   p.g = *g;
   p.amax_rec = nullptr;

@@ -21,35 +21,8 @@
 //     MFMA of the register-staged kernel on the K <= 64 layers.
 // Per-row validity is a bit mask (bit dz | bit 8+dy | bit 16+dx set when that tap coordinate is inside the image),
 // tested against a per-step `need` word: 3 VALU per piece instead of a compare chain.
-#include "conv_common.h"
+#include "conv_tiles.h"
 #include <type_traits>
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-#define DMA_OOB 0x7ffffff0
-// LP ("low precision", BASELINE.json configs[1]): ONE bf16 plane per operand and one v_mfma_f32_32x32x16_bf16 per fragment pair
-// instead of the (hi, lo) fp16 planes and three products: a third of the matrix instructions, half of the DMA pieces and of
-// the LDS traffic; fp32 accumulators, bias / residual / output stay fp32; no scale (bf16 has the fp32 exponent range).
-template <bool LP>
-__device__ __forceinline__ f32x16 mfma_16(half8 a, half8 b, f32x16 c) {
-  if constexpr (LP) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int4v rsrc_words(const void* ptr, unsigned bytes) {
-  uint64_t a = reinterpret_cast<uint64_t>(ptr);
-  int4v r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu));
-  r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-  r.w = 0x00020000;
-  return r;
-}
-// one 1-KiB piece: lane l's 16 bytes at buffer offset `off` land at LDS byte address lds_dst + 16*l
-__device__ __forceinline__ void dma_piece(int4v rsrc, int off, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" : : "v"(off), "s"(lds_dst), "s"(rsrc) : "memory");
-}
 
 template <int BM, int BN, int WM, int WN, int NS, bool UNIFORM_DX, bool LP>
 __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __restrict__ xh, const _Float16* __restrict__ xl,
@@ -76,7 +49,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
     // ================================================================== producer waves
     // producer q owns tile rows [q*BM/4, +BM/4) of A and [q*BN/4, +BN/4) of B; lane l of piece i covers row 16*i + (l >> 2)
     const int pq = wave - WM * WN;
-    int4v rxh = rsrc_words(xh, x_bytes), rxl = rsrc_words(xl, x_bytes), rwh = rsrc_words(wh, w_bytes), rwl = rsrc_words(wl, w_bytes);
+    int4v rxh = cv_rsrc(xh, x_bytes), rxl = cv_rsrc(xl, x_bytes), rwh = cv_rsrc(wh, w_bytes), rwl = cv_rsrc(wl, w_bytes);
     asm volatile("s_nop 4" : "+s"(rxh), "+s"(rxl), "+s"(rwh), "+s"(rwl));
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
     const int prow = lane >> 2;
@@ -84,7 +57,8 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
     int a_off[AP], b_off[BP];
     unsigned a_mask[AP];
     bool b_ok[BP];
-    // inside-the-image bits of the taps t in [0, k) for a coordinate c0 + t in [0, n)
+    // inside-the-image bits of the taps t in [0, k) for a coordinate c0 + t in [0, n) (also in conv_h3t.hip; as a shared function it moved a wait in
+    // the !UNIFORM_DX single-plane kernels, profiles/conv_tiles_header.md)
     auto tap_bits = [](int c0, int k, int n) -> unsigned {
       int lo = c0 < 0 ? -c0 : 0, hi = n - c0 < k ? n - c0 : k;
       return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
@@ -131,18 +105,18 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
       const unsigned pa_dst = lds0 + stage * STAGE + pq * (BM / 4) * 64, pb_dst = lds0 + stage * STAGE + B_HI + pq * (BN / 4) * 64;
 #pragma unroll
       for (int i = 0; i < AP; ++i) {
-        const int off = ((a_mask[i] & need) == need) ? a_off[i] + x_uni : DMA_OOB;
+        const int off = ((a_mask[i] & need) == need) ? a_off[i] + x_uni : CV_OOB;
         if (no_dma) continue;
-        dma_piece(rxh, off, pa_dst + i * 1024);
-        if (!LP) dma_piece(rxl, off, pa_dst + A_LO + i * 1024);
+        cv_piece(rxh, off, pa_dst + i * 1024);
+        if (!LP) cv_piece(rxl, off, pa_dst + A_LO + i * 1024);
       }
       const bool r_ok = live && (s_chunk * 32 + c8 < p.R);
 #pragma unroll
       for (int i = 0; i < BP; ++i) {
-        const int off = (b_ok[i] && r_ok) ? b_off[i] + w_uni : DMA_OOB;
+        const int off = (b_ok[i] && r_ok) ? b_off[i] + w_uni : CV_OOB;
         if (no_dma) continue;
-        dma_piece(rwh, off, pb_dst + i * 1024);
-        if (!LP) dma_piece(rwl, off, pb_dst + BN * 64 + i * 1024);
+        cv_piece(rwh, off, pb_dst + i * 1024);
+        if (!LP) cv_piece(rwl, off, pb_dst + BN * 64 + i * 1024);
       }
       if (!live) return;
       ++s_chunk;
@@ -210,54 +184,24 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
     }
   };
   f32x16 acc[TM][TN];
-  auto mfma_set = [&](auto SET) {
+  auto mfma_set = [&](auto SET) {          // the weight fragment is the row operand: acc is [channel][pixel]
     constexpr int B = decltype(SET)::value;
-    if constexpr (!LP) {
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<false>(fbh[B][b], fal[B][a], acc[a][b]);
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<false>(fbl[B][b], fah[B][a], acc[a][b]);
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<LP>(fbh[B][b], fah[B][a], acc[a][b]);
+    cv_mfma_set<LP, false>(acc, fah[B], fal[B], fbh[B], fbl[B]);
   };
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
   // the fragment reads of the next half-step are dealt out behind the MFMAs of this one (conv_h3t.hip has the measurement)
-  constexpr int NRD = NPL * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN, RPM = (NRD + NMF - 1) / NMF;
-  auto interleave = [&]() {
-#pragma unroll
-    for (int i = 0; i < NMF; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      if (i * RPM < NRD) __builtin_amdgcn_sched_group_barrier(0x100, RPM, 0);
-    }
-  };
+  constexpr int NRD = NPL * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN;
   const float inv = LP ? 1.0f : 1.0f / (sx[0] * sw[0]);
   int stage = 0;
-  // WDNO_DBG_STAMP_CYCLES / _EPILOGUE / _REALTIME (tools/bench_conv.py --stamps): the amax record carries this wave's shader cycles in the kernel / in
-  // the tile epilogues / its 100 MHz wall ticks instead of max|y|
-  const int sdbg = p.debug >= WDNO_DBG_NO_DMA_OFFSET ? p.debug - WDNO_DBG_NO_DMA_OFFSET : p.debug;      // the same stamp with the DMA issue switched off (WDNO_DBG_NO_DMA)
-  const bool stamps = sdbg == WDNO_DBG_STAMP_CYCLES || sdbg == WDNO_DBG_STAMP_EPILOGUE || sdbg == WDNO_DBG_STAMP_REALTIME;
-  const uint64_t c_begin = stamps ? __builtin_amdgcn_s_memtime() : 0, r_begin = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-  uint64_t c_epi = 0;
+  CvStamps stamps = cv_stamps_begin(p.debug);                    // tools/bench_conv.py --stamps
   for (int t = 0; t < my_tiles; ++t) {
     const int tile = xcd_swizzle((int)blockIdx.x + t * (int)gridDim.x, p.ntiles);
     const int tile_m = tile / p.tiles_n, tile_n = tile - tile_m * p.tiles_n;
     const int64_t m0 = (int64_t)tile_m * BM;
     const int n0 = tile_n * BN;
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TN; ++b)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-    lgkm0_barrier();
+    cv_zero_acc(acc);
+    cv_lgkm0_barrier();
     read_frags(B0{}, stage, 0);
     // The last step is peeled: with the barrier + next-stage reads under a condition, the two paths into the second MFMA
     // group carry different numbers of outstanding LDS reads and the compiler's s_waitcnt has to assume the smaller one --
@@ -265,26 +209,27 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
     for (int step = 0; step + 1 < p.nsteps; ++step) {
       read_frags(B1{}, stage, 1);
       mfma_set(B0{});
-      interleave();
+      cv_interleave<NRD, NMF>();
       __builtin_amdgcn_sched_barrier(0);
       stage = stage + 1 == NS ? 0 : stage + 1;
-      lgkm0_barrier();
+      cv_lgkm0_barrier();
       read_frags(B0{}, stage, 0);
       mfma_set(B1{});
-      interleave();
+      cv_interleave<NRD, NMF>();
       __builtin_amdgcn_sched_barrier(0);
     }
     read_frags(B1{}, stage, 1);
     mfma_set(B0{});
-    interleave();
+    cv_interleave<NRD, NMF>();
     __builtin_amdgcn_sched_barrier(0);
     stage = stage + 1 == NS ? 0 : stage + 1;
     mfma_set(B1{});
     __builtin_amdgcn_sched_barrier(0);
-    const uint64_t e_begin = stamps ? __builtin_amdgcn_s_memtime() : 0;
+    const uint64_t e_begin = stamps.on ? __builtin_amdgcn_s_memtime() : 0;
     // epilogue of this tile (the producers are already fetching the next one). The MFMAs are issued with the weight
     // fragment as the row operand, so the accumulator tile is [channel][pixel]: lane li owns ONE pixel and holds runs of
-    // four consecutive channels -> 16-byte stores and one output-row computation per lane and tile row block.
+    // four consecutive channels -> 16-byte stores and one output-row computation per lane and tile row block. (The same lines close conv_h3t.hip's
+    // tile; inline in both: as a function the whole kernel is allocated differently, single-plane kernels get 20 B of scratch, profiles/conv_tiles_header.md)
 #pragma unroll
     for (int a = 0; a < TM; ++a) {
       const int64_t pm = m0 + m_base + a * 32 + li;
@@ -308,7 +253,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
               va.x += ta.x; va.y += ta.y; va.z += ta.z; va.w += ta.w;
               if (k0 + 8 < g.K) { const float4 tb = *reinterpret_cast<const float4*>(bias + kb); vb.x += tb.x; vb.y += tb.y; vb.z += tb.z; vb.w += tb.w; }
             }
-            const uint4 o = bf16x8_from_runs(va, vb);
+            const uint4 o = cv_bf16x8_from_runs(va, vb);
             if (k0 + 8 * hh < g.K) *reinterpret_cast<uint4*>(y16 + k0 + 8 * hh) = o;
             am = amax4(amax4(am, va), vb);
           }
@@ -330,9 +275,9 @@ __global__ __launch_bounds__(512) void conv_fwd_h3d_kernel(const _Float16* __res
         }
       }
     }
-    if (stamps) c_epi += __builtin_amdgcn_s_memtime() - e_begin;
+    if (stamps.on) stamps.c_epi += __builtin_amdgcn_s_memtime() - e_begin;
   }
-  if (stamps) am = sdbg == WDNO_DBG_STAMP_CYCLES ? (float)(__builtin_amdgcn_s_memtime() - c_begin) : sdbg == WDNO_DBG_STAMP_EPILOGUE ? (float)c_epi : (float)(__builtin_amdgcn_s_memrealtime() - r_begin);
+  if (stamps.on) am = cv_stamps_value(stamps);
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * (WM * WN) + wave);
 }
 
@@ -409,7 +354,7 @@ int wdno_conv_fwd_h3_dma_choose(const ConvP& p, bool lp, ConvFwdChoice& c) {
   const int64_t nt = cdiv64(p.P, bm) * cdiv(g.K, bn);
   const int64_t x_elems = (int64_t)g.N * g.D * g.H * g.W * g.C;
   const int64_t w_elems = (int64_t)g.kd * g.kh * g.K * p.R;
-  if (nt > 0x7fffffff || x_elems * 2 >= DMA_OOB || w_elems * 2 >= DMA_OOB || p.P >= 0x7fffffff) return WDNO_EUNSUPPORTED;
+  if (nt > 0x7fffffff || x_elems * 2 >= CV_OOB || w_elems * 2 >= CV_OOB || p.P >= 0x7fffffff) return WDNO_EUNSUPPORTED;
   c.kw = g.kw; c.sp = 0;
   c.plan.family = WDNO_CONV_CHUNKED_H3D;
   c.plan.bm = bm; c.plan.bn = bn;

@@ -27,32 +27,8 @@
 //     252 K cycles at a 1.41 GHz clock: what is left is the package power limit, see profiles/r04_conv_limiter.md.)
 // Arithmetic, operand formats, weight pack and epilogue are those of conv_h3d.hip; the fp32 accumulation order differs
 // (dz, dy, channel block, dx instead of dz, dy, dx, channel block), so the two agree to rounding, not bit for bit.
-#include "conv_common.h"
+#include "conv_tiles.h"
 #include <type_traits>
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-#define T_OOB 0x7ffffff0
-
-template <bool LP>
-__device__ __forceinline__ f32x16 t_mfma(half8 a, half8 b, f32x16 c) {
-  if constexpr (LP) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int4v t_rsrc(const void* ptr, unsigned bytes) {
-  uint64_t a = reinterpret_cast<uint64_t>(ptr);
-  int4v r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu));
-  r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-  r.w = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void t_piece(int4v rsrc, int off, unsigned lds_dst) {
-  lds_dst = __builtin_amdgcn_readfirstlane(lds_dst);      // (wave-uniform by construction; with nine pieces per wave the compiler kept it in a vector register)
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" : : "v"(off), "s"(lds_dst), "s"(rsrc) : "memory");
-}
 
 // Which tap rows (dz, dy) of a tile can contribute at all (ConvP::zb_*): bit dz of z[c] / bit dy of y[c] = some output pixel of the tile has its
 // source plane / source row inside the grid AND, for class c = 0 (the channel blocks that obey the zero box), in front of the box. A tile
@@ -149,7 +125,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
   if (wave >= WM * WN) {
     // ================================================================== producer waves
     const int pq = wave - WM * WN;
-    int4v rxh = t_rsrc(xh, x_bytes), rxl = t_rsrc(xl, x_bytes), rwh = t_rsrc(wh, w_bytes), rwl = t_rsrc(wl, w_bytes);
+    int4v rxh = cv_rsrc(xh, x_bytes), rxl = cv_rsrc(xl, x_bytes), rwh = cv_rsrc(wh, w_bytes), rwl = cv_rsrc(wl, w_bytes);
     asm volatile("s_nop 4" : "+s"(rxh), "+s"(rxl), "+s"(rwh), "+s"(rwl));
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
     // lane -> (row of the piece, logical 16-byte chunk): the XOR swizzle of the fragment reads applied on the source side. 64-byte rows:
@@ -159,7 +135,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
     int a_off[PA], b_off[PB];
     unsigned a_mask[PA];
     bool b_ok[PB];
-    auto tap_bits = [](int c0, int k, int n) -> unsigned {
+    auto tap_bits = [](int c0, int k, int n) -> unsigned {          // (as conv_h3d.hip, which says why it is no shared function)
       int lo = c0 < 0 ? -c0 : 0, hi = n - c0 < k ? n - c0 : k;
       return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
     };
@@ -229,18 +205,18 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
 #pragma unroll
       for (int i = 0; i < PA; ++i) {
         if (pq + 4 * i >= S::APIECES) continue;                    // compile-time for all but the last i
-        const int off = ((a_mask[i] & need) == need) ? a_off[i] + x_uni : T_OOB;
+        const int off = ((a_mask[i] & need) == need) ? a_off[i] + x_uni : CV_OOB;
         if (no_dma) continue;
-        t_piece(rxh, off, dst + i * 4096);
-        if (!LP) t_piece(rxl, off, dst + A_LO + i * 4096);
+        cv_piece<true>(rxh, off, dst + i * 4096);
+        if (!LP) cv_piece<true>(rxl, off, dst + A_LO + i * 4096);
       }
 #pragma unroll
       for (int i = 0; i < PB; ++i) {
         if (pq + 4 * i >= S::BPIECES) continue;                    // (the 14 weight pieces of the 7-wide stem are not a multiple of four)
-        const int off = b_ok[i] && !pad ? b_off[i] + w_uni : T_OOB;
+        const int off = b_ok[i] && !pad ? b_off[i] + w_uni : CV_OOB;
         if (no_dma) continue;
-        t_piece(rwh, off, dst + B_HI + i * 4096);
-        if (!LP) t_piece(rwl, off, dst + B_LO + i * 4096);
+        cv_piece<true>(rwh, off, dst + B_HI + i * 4096);
+        if (!LP) cv_piece<true>(rwl, off, dst + B_LO + i * 4096);
       }
       if (skipping) {
         ++s_cnt;
@@ -320,27 +296,9 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
     }
   };
   f32x16 acc[TM][TN];
-  auto mfma_set = [&](int set) {
-    if constexpr (!LP) {
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = t_mfma<false>(fbh[set][b], fal[set][a], acc[a][b]);
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = t_mfma<false>(fbl[set][b], fah[set][a], acc[a][b]);
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TN; ++b) acc[a][b] = t_mfma<LP>(fbh[set][b], fah[set][a], acc[a][b]);
-  };
+  auto mfma_set = [&](int set) { cv_mfma_set<LP, false>(acc, fah[set], fal[set], fbh[set], fbl[set]); };      // weight fragment = row operand: acc is [channel][pixel]
   const float inv = LP ? 1.0f : 1.0f / (sx[0] * sw[0]);
-  const int sdbg = p.debug >= WDNO_DBG_NO_DMA_OFFSET ? p.debug - WDNO_DBG_NO_DMA_OFFSET : p.debug;
-  const bool stamps = sdbg == WDNO_DBG_STAMP_CYCLES || sdbg == WDNO_DBG_STAMP_EPILOGUE || sdbg == WDNO_DBG_STAMP_REALTIME;     // see conv_h3d.hip
-  const uint64_t c_begin = stamps ? __builtin_amdgcn_s_memtime() : 0, r_begin = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-  uint64_t c_epi = 0;
+  CvStamps stamps = cv_stamps_begin(p.debug);                    // tools/bench_conv.py --stamps
   int boff = 0;                                                   // byte offset of the stage being read
   for (int t = 0; t < my_tiles; ++t) {
     const int vt = xcd_swizzle((int)blockIdx.x + t * (int)gridDim.x, nvt);
@@ -372,20 +330,12 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
       for (int b = 0; b < TN; ++b)
 #pragma unroll
         for (int e = 0; e < 16; ++e) asm volatile("v_mov_b32 %0, 0" : "=v"(acc[a][b][e]));   // not `= 0.f`: the 7-wide kernel kept a second,
-    lgkm0_barrier();                                                                          // loop-invariant set of 64 zero registers to start each tile from
+    cv_lgkm0_barrier();                                                                          // loop-invariant set of 64 zero registers to start each tile from
     read_frags(0, boff, 0, 0);
     // One scheduling region per sub-step: the fragment reads of the NEXT sub-step are dealt one per MFMA of this one (not all reads
     // first, the order the kernel was first written in) -- a wave issues in order, so a block of 8 ds_read_b128 ahead
     // of the MFMAs adds its issue time (the LDS is also serving the other three compute waves) to every sub-step.
-    constexpr int NRD = NPL * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN;
-    constexpr int RPM = (NRD + NMF - 1) / NMF;                     // reads behind each MFMA until they are used up
-    auto interleave = [&]() {
-#pragma unroll
-      for (int i = 0; i < NMF; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if (i * RPM < NRD) __builtin_amdgcn_sched_group_barrier(0x100, RPM, 0);
-      }
-    };
+    constexpr int NRD = NPL * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN;      // (cv_interleave: RPM reads behind each MFMA until they are used up)
     // a stage: sub-step `sub` (dx = sub / KSN, ks = sub % KSN) works on fragment set (PAR + sub) & 1 while the reads of sub + 1 -- at the
     // last sub-step, behind the barrier, the first reads of the next stage -- go to the other set. With an odd number of sub-steps
     // (7-wide taps on 16-channel blocks) the starting set alternates from stage to stage.
@@ -398,11 +348,11 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
           read_frags((PAR + sub + 1) & 1, boff, (sub + 1) / KSN, (sub + 1) % KSN);
         } else if (!LAST) {
           boff = STAGE - boff;
-          lgkm0_barrier();
+          cv_lgkm0_barrier();
           read_frags((PAR + NSUB) & 1, boff, 0, 0);
         }
         mfma_set((PAR + sub) & 1);
-        if (sub + 1 < NSUB || !LAST) interleave();
+        if (sub + 1 < NSUB || !LAST) cv_interleave<NRD, NMF>();
         __builtin_amdgcn_sched_barrier(0);
       }
     };
@@ -469,8 +419,8 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
           for (int e = 0; e < 16; ++e) acc[a][b][e] += acc2[a][b][e];
     }
     boff = STAGE - boff;
-    const uint64_t e_begin = stamps ? __builtin_amdgcn_s_memtime() : 0;
-    // epilogue: as conv_h3d.hip (accumulator tile is [channel][pixel]: a lane owns one pixel and runs of four channels)
+    const uint64_t e_begin = stamps.on ? __builtin_amdgcn_s_memtime() : 0;
+    // epilogue: as conv_h3d.hip (accumulator tile is [channel][pixel]: a lane owns one pixel and runs of four channels), inline for the reason given there
 #pragma unroll
     for (int a = 0; a < TM; ++a) {
       const int64_t pm = m0 + m_base + a * 32 + li;
@@ -506,7 +456,7 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
               va.x += ta.x; va.y += ta.y; va.z += ta.z; va.w += ta.w;
               if (k0 + 8 < g.K) { const float4 tb = *reinterpret_cast<const float4*>(bias + kb); vb.x += tb.x; vb.y += tb.y; vb.z += tb.z; vb.w += tb.w; }
             }
-            const uint4 o = bf16x8_from_runs(va, vb);
+            const uint4 o = cv_bf16x8_from_runs(va, vb);
             if (k0 + 8 * hh < g.K) *reinterpret_cast<uint4*>(y16 + k0 + 8 * hh) = o;
             am = amax4(amax4(am, va), vb);
           }
@@ -528,9 +478,9 @@ __global__ __launch_bounds__(512) void conv_fwd_h3t_kernel(const _Float16* __res
         }
       }
     }
-    if (stamps) c_epi += __builtin_amdgcn_s_memtime() - e_begin;
+    if (stamps.on) stamps.c_epi += __builtin_amdgcn_s_memtime() - e_begin;
   }
-  if (stamps) am = sdbg == WDNO_DBG_STAMP_CYCLES ? (float)(__builtin_amdgcn_s_memtime() - c_begin) : sdbg == WDNO_DBG_STAMP_EPILOGUE ? (float)c_epi : (float)(__builtin_amdgcn_s_memrealtime() - r_begin);
+  if (stamps.on) am = cv_stamps_value(stamps);
   if (p.amax_rec) wave_amax_emit(am, p.amax_rec, (int)blockIdx.x * (WM * WN) + wave);
 }
 
@@ -625,7 +575,7 @@ int wdno_conv_fwd_h3_tap_choose(int shape, int tsplit, const ConvP& p, bool lp, 
   const int64_t nt = cdiv64(p.P, bm) * cdiv(g.K, bn);
   const int64_t x_elems = (int64_t)g.N * g.D * g.H * g.W * g.C;
   const int64_t w_elems = (int64_t)g.kd * g.kh * g.K * p.R;
-  if (nt > 0x7fffffff || x_elems * 2 >= T_OOB || w_elems * 2 >= T_OOB || p.P >= 0x7fffffff - bm) return WDNO_EUNSUPPORTED;
+  if (nt > 0x7fffffff || x_elems * 2 >= CV_OOB || w_elems * 2 >= CV_OOB || p.P >= 0x7fffffff - bm) return WDNO_EUNSUPPORTED;
   c.plan.bm = bm; c.plan.bn = bn;
   c.plan.uniform = 1;
   c.plan.ksplit = 1;

@@ -1,14 +1,14 @@
 // conv_wgrad_h3d.hip -- weight gradient, 3 x fp16 split, operands streamed by LDS-DMA (gfx950).
 //
 // dwp[tap][k][r] = sum_p dy[p][k] * x[p shifted by tap][r]  (r = dx*C + c), same arithmetic and workspace contract as
-// conv_wgrad_h3_kernel (conv_h3.hip). Structure = the forward DMA kernel's (conv_h3d.hip):
+// conv_wgrad_h3_kernel (conv_wgrad_h3.hip). Structure = the forward DMA kernel's (conv_h3d.hip):
 //   * persistent 512-thread blocks, one per CU: waves 0-3 compute (2 x 2 over the BM x BN tile), waves 4-7 produce;
 //   * NS-stage LDS ring, one barrier per 32-pixel step, hand-counted vmcnt so the pieces of later steps stay in flight;
 //   * work items (k tile, tap row, r tile, pixel split) are walked in a fixed order, every item has the same number of
 //     steps (pixels past the end contribute zeros), so producers and consumers count steps without talking.
 // What is specific to the weight gradient:
 //   * both operands are pixel-major in memory while the MFMA wants 8 consecutive pixels per lane -> fragments are read
-//     with ds_read_b64_tr_b16 (see conv_h3.hip). The LDS plane layout is [4-pixel group][64-byte unit = 32 channels]
+//     with ds_read_b64_tr_b16 (see conv_wgrad_h3.hip). The LDS plane layout is [4-pixel group][64-byte unit = 32 channels]
 //     [pixel in group][64 B]. A DMA piece is lane-linear (lane L lands at +16 L), so the LDS layout IS the lane -> address
 //     map of the fetch: here four consecutive lanes fetch 64 contiguous bytes of one pixel row and a piece is 4 pixels x
 //     256 contiguous bytes. (The first layout, [group][16-byte chunk][pixel][16 B], put four different pixels into every
@@ -21,19 +21,8 @@
 //     queue as the pieces.
 //   * the accumulator tile is kept as [r][k] (x fragment as the MFMA row operand), so a lane owns one k and runs of four
 //     consecutive r: 16-byte stores into dwp / the split workspace.
-#include "conv_common.h"
+#include "conv_tiles.h"
 #include <type_traits>
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-#define WD_OOB 0x7ffffff0
-// LP = single bf16 plane per operand, one product (see conv_h3d.hip); !LP = (hi, lo) fp16 planes, three products
-template <bool LP>
-__device__ __forceinline__ f32x16 mfma_16(half8 a, half8 b, f32x16 c) {
-  if constexpr (LP) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
 
 struct WgradDP {
   ConvP c;
@@ -44,23 +33,6 @@ struct WgradDP {
   int splitpair, n_a;                       // window kernel: the odd tap row paired across two pixel splits (items >= n_a), see conv_wgrad_h3w_kernel
 };
 
-__device__ __forceinline__ int4v wd_rsrc(const void* ptr, unsigned bytes) {
-  uint64_t a = reinterpret_cast<uint64_t>(ptr);
-  int4v r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu));
-  r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-  r.w = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void wd_piece(int4v rsrc, int off, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" : : "v"(off), "s"(lds_dst), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ int4v wd_load_rec(int4v rsrc, int off) {
-  int4v v;
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(v) : "v"(off), "s"(rsrc) : "memory");
-  return v;
-}
 // transpose-read fragment: channels ch0..ch0+31 (MFMA row/column index = lane & 31) x pixels pix0..pix0+15 (k index) of a
 // plane laid out [pixel / 4][chunk16][pixel % 4][16 B] with NCH chunks per pixel
 template <int NCH>
@@ -126,8 +98,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3d_kernel(const _Float16* __r
   if (wave >= 4) {
     // ================================================================== producer waves
     const int pq = wave - 4;
-    int4v rxh = wd_rsrc(xh, x_bytes), rxl = wd_rsrc(xl, x_bytes), rdh = wd_rsrc(dyh, dy_bytes), rdl = wd_rsrc(dyl, dy_bytes);
-    int4v rtb = wd_rsrc(table, tbl_bytes);
+    int4v rxh = cv_rsrc(xh, x_bytes), rxl = cv_rsrc(xl, x_bytes), rdh = cv_rsrc(dyh, dy_bytes), rdl = cv_rsrc(dyl, dy_bytes);
+    int4v rtb = cv_rsrc(table, tbl_bytes);
     asm volatile("s_nop 4" : "+s"(rxh), "+s"(rxl), "+s"(rdh), "+s"(rdl), "+s"(rtb));
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
     // pair j of this producer = global pair pq + 4*j: pairs [0, APC) are dy pieces, [APC, NPAIR) are x pieces.
@@ -185,7 +157,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3d_kernel(const _Float16* __r
       for (int j = 0; j < R; ++j) {
         const int pm = r_pbeg + rc.s * 32 + row[j];
         rok[S][j] = live && pm < (int)p.P;
-        rec[S][j] = wd_load_rec(rtb, rok[S][j] ? pm * 16 : WD_OOB);
+        rec[S][j] = cv_load_b128(rtb, rok[S][j] ? pm * 16 : CV_OOB);
       }
       if (live && ++rc.s == wp.nsteps) { rc.s = 0; if (++rc.t < my_items) load_item_r(); }
     };
@@ -205,15 +177,15 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3d_kernel(const _Float16* __r
         const bool ok0 = live && rok[S][j] && i_ok[j];
         if (no_piece) continue;
         if (gp < APC) {
-          const int off = ok0 ? e.x * k2 + i_off[j] : WD_OOB;
-          wd_piece(rdh, off, sb + gp * 1024);
-          if (!LP) wd_piece(rdl, off, sb + A_LO + gp * 1024);
+          const int off = ok0 ? e.x * k2 + i_off[j] : CV_OOB;
+          cv_piece(rdh, off, sb + gp * 1024);
+          if (!LP) cv_piece(rdl, off, sb + A_LO + gp * 1024);
         } else {
           const int d = (e.z >> 16) + c_dz, h = (int)(short)(e.z & 0xffff) + c_dy, w = e.w + i_dx[j];
           const bool ok = ok0 && (unsigned)d < (unsigned)g.D && (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)g.W;
-          const int off = ok ? (e.y + c_tapoff + i_off[j]) * 2 : WD_OOB;
-          wd_piece(rxh, off, sb + B_HI + (gp - APC) * 1024);
-          if (!LP) wd_piece(rxl, off, sb + B_LO + (gp - APC) * 1024);
+          const int off = ok ? (e.y + c_tapoff + i_off[j]) * 2 : CV_OOB;
+          cv_piece(rxh, off, sb + B_HI + (gp - APC) * 1024);
+          if (!LP) cv_piece(rxl, off, sb + B_LO + (gp - APC) * 1024);
         }
       }
       if (live && ++pc.s == wp.nsteps) { pc.s = 0; if (++pc.t < my_items) load_item_p(); }
@@ -297,62 +269,37 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3d_kernel(const _Float16* __r
   f32x16 acc[TM][TN];
   auto mfma_set = [&](auto SET) {          // row operand = x fragment (r), column operand = dy fragment (k): acc is [r][k]
     constexpr int B = decltype(SET)::value;
-    if constexpr (!LP) {
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<false>(fbh[B][b], fal[B][a], acc[a][b]);
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<false>(fbl[B][b], fah[B][a], acc[a][b]);
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<LP>(fbh[B][b], fah[B][a], acc[a][b]);
+    cv_mfma_set<LP, false>(acc, fah[B], fal[B], fbh[B], fbl[B]);
   };
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
   // one scheduling region per half-step: the transpose reads of the next fragments are dealt out behind the MFMAs of the
   // current ones (conv_h3t.hip has the measurement), RPM reads per MFMA until they are used up
-  constexpr int NRD = NPL * 2 * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN, RPM = (NRD + NMF - 1) / NMF;
-  auto interleave = [&]() {
-#pragma unroll
-    for (int i = 0; i < NMF; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      if (i * RPM < NRD) __builtin_amdgcn_sched_group_barrier(0x100, RPM, 0);
-    }
-  };
+  constexpr int NRD = NPL * 2 * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN;
   const float inv = LP ? 1.0f : 1.0f / (sx[0] * sdy[0]);
   const int hh = lane >> 5;
   int stage = 0;
   for (int t = 0; t < my_items; ++t) {
     int tile_k, tap, tile_r, split;
     decode_item(t, tile_k, tap, tile_r, split);
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TN; ++b)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-    lgkm0_barrier();
+    cv_zero_acc(acc);
+    cv_lgkm0_barrier();
     read_frags(B0{}, stage, 0);
     for (int step = 0; step + 1 < wp.nsteps; ++step) {      // last step peeled, see conv_h3d.hip
       read_frags(B1{}, stage, 1);
       mfma_set(B0{});
-      interleave();
+      cv_interleave<NRD, NMF>();
       __builtin_amdgcn_sched_barrier(0);
       stage = stage + 1 == NS ? 0 : stage + 1;
-      lgkm0_barrier();
+      cv_lgkm0_barrier();
       read_frags(B0{}, stage, 0);
       mfma_set(B1{});
-      interleave();
+      cv_interleave<NRD, NMF>();
       __builtin_amdgcn_sched_barrier(0);
     }
     read_frags(B1{}, stage, 1);
     mfma_set(B0{});
-    interleave();
+    cv_interleave<NRD, NMF>();
     __builtin_amdgcn_sched_barrier(0);
     stage = stage + 1 == NS ? 0 : stage + 1;
     mfma_set(B1{});
@@ -463,8 +410,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3w_kernel(const _Float16* __r
   if (wave >= 4) {
     // ================================================================== producer waves
     const int pq = wave - 4;
-    int4v rxh = wd_rsrc(xh, x_bytes), rxl = wd_rsrc(xl, x_bytes), rdh = wd_rsrc(dyh, dy_bytes), rdl = wd_rsrc(dyl, dy_bytes);
-    int4v rtb = wd_rsrc(table, tbl_bytes);
+    int4v rxh = cv_rsrc(xh, x_bytes), rxl = cv_rsrc(xl, x_bytes), rdh = cv_rsrc(dyh, dy_bytes), rdl = cv_rsrc(dyl, dy_bytes);
+    int4v rtb = cv_rsrc(table, tbl_bytes);
     asm volatile("s_nop 4" : "+s"(rxh), "+s"(rxl), "+s"(rdh), "+s"(rdl), "+s"(rtb));
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
     auto producer = [&](auto RC, auto KBC) {
@@ -530,7 +477,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3w_kernel(const _Float16* __r
         for (int j = 0; j < R; ++j) {
           const int pm = r_pbeg[slot[j]] + rc.s * 32 + row[j] - (pq + 4 * j < APCT ? 0 : g.pw);
           rok[S][j] = live && pm >= 0 && pm < (int)p.P;
-          rec[S][j] = wd_load_rec(rtb, rok[S][j] ? pm * 16 : WD_OOB);
+          rec[S][j] = cv_load_b128(rtb, rok[S][j] ? pm * 16 : CV_OOB);
         }
         if (live && ++rc.s == wp.nsteps) { rc.s = 0; if (++rc.t < my_items) load_item_r(); }
       };
@@ -546,17 +493,17 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3w_kernel(const _Float16* __r
           const int gp = pq + 4 * j;                                    // pq is wave-uniform: scalar branches
           const bool ok0 = live && rok[S][j] && i_ok[j];
           if (gp < APCT) {
-            const int off = ok0 ? e.x * k2 + i_off[j] : WD_OOB;
+            const int off = ok0 ? e.x * k2 + i_off[j] : CV_OOB;
             const unsigned dst = sb + (gp / APC) * A_PLANE + (gp % APC) * 1024;
-            wd_piece(rdh, off, dst);
-            if (!LP) wd_piece(rdl, off, dst + A_LO);
+            cv_piece(rdh, off, dst);
+            if (!LP) cv_piece(rdl, off, dst + A_LO);
           } else {
             const int s2 = gp - APCT < WPC ? 0 : 1;
             const int d = (e.z >> 16) + c_dz[s2], h = (int)(short)(e.z & 0xffff) + c_dy[s2];
             const bool ok = ok0 && c_on[s2] && (unsigned)d < (unsigned)g.D && (unsigned)h < (unsigned)g.H;
-            const int off = ok ? (e.y + c_tapoff[s2] + i_off[j]) * 2 : WD_OOB;
-            wd_piece(rxh, off, sb + B_HI + (gp - APCT) * 1024);
-            if (!LP) wd_piece(rxl, off, sb + B_LO + (gp - APCT) * 1024);
+            const int off = ok ? (e.y + c_tapoff[s2] + i_off[j]) * 2 : CV_OOB;
+            cv_piece(rxh, off, sb + B_HI + (gp - APCT) * 1024);
+            if (!LP) cv_piece(rxl, off, sb + B_LO + (gp - APCT) * 1024);
           }
         }
         if (live && ++pc.s == wp.nsteps) { pc.s = 0; if (++pc.t < my_items) load_item_p(); }
@@ -683,29 +630,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3w_kernel(const _Float16* __r
     f32x16 acc[TM][TN];
     auto mfma_set = [&](auto SET) {          // row operand = x fragment (column tile), column operand = dy fragment (k): acc is [r][k]
       constexpr int B = decltype(SET)::value;
-      if constexpr (!LP) {
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-          for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<false>(fbh[B][b], fal[B][a], acc[a][b]);
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-          for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<false>(fbl[B][b], fah[B][a], acc[a][b]);
-      }
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<LP>(fbh[B][b], fah[B][a], acc[a][b]);
+      cv_mfma_set<LP, false>(acc, fah[B], fal[B], fbh[B], fbl[B]);
     };
-    constexpr int NRD = NPL * 2 * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN, RPM = (NRD + NMF - 1) / NMF;
-    auto interleave = [&]() {
-#pragma unroll
-      for (int i = 0; i < NMF; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if (i * RPM < NRD) __builtin_amdgcn_sched_group_barrier(0x100, RPM, 0);
-      }
-    };
+    constexpr int NRD = NPL * 2 * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN;
     using B0 = std::integral_constant<int, 0>;
     using B1 = std::integral_constant<int, 1>;
     int stage = 0;
@@ -721,9 +648,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3w_kernel(const _Float16* __r
 #pragma unroll
         for (int b = 0; b < TN; ++b)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+          for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;      // (not cv_zero_acc: four to six scalar instructions fewer in this kernel, profiles/conv_tiles_header.md)
       select(0); select(1);
-      lgkm0_barrier();
+      cv_lgkm0_barrier();
       read_frags(B0{}, stage, 0);
       advance(0); advance(1);
       for (int step = 0; step + 1 < wp.nsteps; ++step) {
@@ -731,21 +658,21 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3w_kernel(const _Float16* __r
         read_frags(B1{}, stage, 1);
         advance(2); advance(3);
         mfma_set(B0{});
-        interleave();
+        cv_interleave<NRD, NMF>();
         __builtin_amdgcn_sched_barrier(0);
         stage = stage + 1 == NS ? 0 : stage + 1;
         select(0); select(1);
-        lgkm0_barrier();
+        cv_lgkm0_barrier();
         read_frags(B0{}, stage, 0);
         advance(0); advance(1);
         mfma_set(B1{});
-        interleave();
+        cv_interleave<NRD, NMF>();
         __builtin_amdgcn_sched_barrier(0);
       }
       select(2); select(3);
       read_frags(B1{}, stage, 1);
       mfma_set(B0{});
-      interleave();
+      cv_interleave<NRD, NMF>();
       __builtin_amdgcn_sched_barrier(0);
       stage = stage + 1 == NS ? 0 : stage + 1;
       mfma_set(B1{});
@@ -829,7 +756,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3s_kernel(const _Float16* __r
   if (wave >= 4) {
     // ================================================================== producer waves: lane = 16-byte slot f of every plane
     const int pq = wave - 4;
-    int4v rxh = wd_rsrc(xh, x_bytes), rxl = wd_rsrc(xl, x_bytes), rdh = wd_rsrc(dyh, dy_bytes), rdl = wd_rsrc(dyl, dy_bytes);
+    int4v rxh = cv_rsrc(xh, x_bytes), rxl = cv_rsrc(xl, x_bytes), rdh = cv_rsrc(dyh, dy_bytes), rdl = cv_rsrc(dyl, dy_bytes);
     asm volatile("s_nop 4" : "+s"(rxh), "+s"(rxl), "+s"(rdh), "+s"(rdl));
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
     const int f = 64 * pq + lane;
@@ -860,12 +787,12 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3s_kernel(const _Float16* __r
     auto issue_next = [&](int buf) {
       const unsigned sb = lds0 + buf * STAGE + pq * 1024;
       const bool xv = x_slot && q >= 0 && q < (int)p.P && (unsigned)(qd + vdz) < (unsigned)g.D && (unsigned)(qh + vdy) < (unsigned)g.H;
-      const int xo = xv && !no_dma ? x_off : WD_OOB;
-      const int d_o = d_slot && dp < (int)p.P && !no_dma ? d_off : WD_OOB;
-      wd_piece(rdh, d_o, sb);
-      if (!LP) wd_piece(rdl, d_o, sb + A_LO);
-      wd_piece(rxh, xo, sb + B_HI);
-      if (!LP) wd_piece(rxl, xo, sb + B_LO);
+      const int xo = xv && !no_dma ? x_off : CV_OOB;
+      const int d_o = d_slot && dp < (int)p.P && !no_dma ? d_off : CV_OOB;
+      cv_piece(rdh, d_o, sb);
+      if (!LP) cv_piece(rdl, d_o, sb + A_LO);
+      cv_piece(rxh, xo, sb + B_HI);
+      if (!LP) cv_piece(rxl, xo, sb + B_LO);
       q += 32; x_off += 32 * g.C * 2; dp += 32; d_off += 32 * g.K * 2;
       qw += 32;
       while (qw >= g.W) { qw -= g.W; if (++qh == g.H) { qh = 0; if (++qd == g.D) qd = 0; } }
@@ -943,29 +870,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3s_kernel(const _Float16* __r
     f32x16 acc[TM][TN];
     auto mfma_set = [&](auto SET) {          // row operand = x fragment (column tile), column operand = dy fragment (k): acc is [r][k]
       constexpr int B = decltype(SET)::value;
-      if constexpr (!LP) {
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-          for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<false>(fbh[B][b], fal[B][a], acc[a][b]);
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-          for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<false>(fbl[B][b], fah[B][a], acc[a][b]);
-      }
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = mfma_16<LP>(fbh[B][b], fah[B][a], acc[a][b]);
+      cv_mfma_set<LP, false>(acc, fah[B], fal[B], fbh[B], fbl[B]);
     };
-    constexpr int NRD = NPL * 2 * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN, RPM = (NRD + NMF - 1) / NMF;
-    auto interleave = [&]() {
-#pragma unroll
-      for (int i = 0; i < NMF; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if (i * RPM < NRD) __builtin_amdgcn_sched_group_barrier(0x100, RPM, 0);
-      }
-    };
+    constexpr int NRD = NPL * 2 * (TM + TN), NMF = (LP ? 1 : 3) * TM * TN;
     using B0 = std::integral_constant<int, 0>;
     using B1 = std::integral_constant<int, 1>;
     int stage = 0;
@@ -980,9 +887,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3s_kernel(const _Float16* __r
 #pragma unroll
         for (int b = 0; b < TN; ++b)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+          for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;      // (not cv_zero_acc: four to six scalar instructions fewer in this kernel, profiles/conv_tiles_header.md)
       select(0); select(1);
-      lgkm0_barrier();
+      cv_lgkm0_barrier();
       read_frags(B0{}, stage, 0);
       advance(0); advance(1);
       for (int step = 0; step + 1 < wp.nsteps; ++step) {
@@ -990,21 +897,21 @@ __global__ __launch_bounds__(512) void conv_wgrad_h3s_kernel(const _Float16* __r
         read_frags(B1{}, stage, 1);
         advance(2); advance(3);
         mfma_set(B0{});
-        interleave();
+        cv_interleave<NRD, NMF>();
         __builtin_amdgcn_sched_barrier(0);
         stage = stage + 1 == NS ? 0 : stage + 1;
         select(0); select(1);
-        lgkm0_barrier();
+        cv_lgkm0_barrier();
         read_frags(B0{}, stage, 0);
         advance(0); advance(1);
         mfma_set(B1{});
-        interleave();
+        cv_interleave<NRD, NMF>();
         __builtin_amdgcn_sched_barrier(0);
       }
       select(2); select(3);
       read_frags(B1{}, stage, 1);
       mfma_set(B0{});
-      interleave();
+      cv_interleave<NRD, NMF>();
       __builtin_amdgcn_sched_barrier(0);
       stage = stage + 1 == NS ? 0 : stage + 1;
       mfma_set(B1{});
@@ -1045,7 +952,7 @@ static bool wd_stem_takes(const wdno_conv_geom* g) {
   return g->sd == 1 && g->sh == 1 && g->sw == 1 && g->OD == g->D && g->OH == g->H && g->OW == g->W && g->kw == 7 && g->pw == 3 &&
          g->C == 48 && (g->K % 8) == 0 && g->K <= 64 && g->kd <= 8 && g->kh <= 8;
 }
-// plan shared by the workspace query and the launch (conv_h3.hip calls both)
+// plan shared by the workspace query and the launch (conv_wgrad_h3.hip calls both)
 void wdno_wgrad_h3d_plan(const wdno_conv_geom* g, int* bm, int* bn, int* splits, int* pix_per_split, int* splitpair) {
   ConvP c;
   fill_params(c, g);
@@ -1166,14 +1073,14 @@ static int wd_choose(const wdno_conv_geom* g, WgradDP& w, int& bm, int& bn, int&
   fill_params(w.c, g);
   wdno_wgrad_h3d_plan(g, &bm, &bn, &w.splits, &w.pix_per_split, &w.splitpair);
   w.n_a = 0x7fffffff;
-  if (w.c.P * 16 >= WD_OOB) return WDNO_EUNSUPPORTED;
+  if (w.c.P * 16 >= CV_OOB) return WDNO_EUNSUPPORTED;
   w.tiles_k = cdiv(g->K, bm);
   w.tiles_r = cdiv(w.c.R, bn);
   w.nsteps = w.pix_per_split / 32;
   w.items = w.tiles_k * w.tiles_r * g->kd * g->kh * w.splits;
   family = WDNO_WGRAD_CHUNKED_H3D;
   if (wd_stem_takes(g)) {
-    if ((int64_t)g->N * g->D * g->H * g->W * g->C * 2 >= WD_OOB || w.c.P * g->K * 2 >= WD_OOB) return WDNO_EUNSUPPORTED;
+    if ((int64_t)g->N * g->D * g->H * g->W * g->C * 2 >= CV_OOB || w.c.P * g->K * 2 >= CV_OOB) return WDNO_EUNSUPPORTED;
     w.tiles_k = w.tiles_r = 1;
     w.items = g->kd * g->kh * w.splits;
     family = WDNO_WGRAD_STEM_H3S;

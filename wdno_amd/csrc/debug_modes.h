@@ -14,9 +14,9 @@
 #define WDNO_DEBUG_MODES(X)                                                                                                                       \
   X(WDNO_DBG_OFF, 0)                    /* production */                                                                                           \
   /* 5 is a list, not one meaning: attention.hip, linattn.hip: thread-per-row softmax / thread-per-token linear-attention kernels, not the MFMA ones; \
-     conv_h3.hip: forward and weight gradient on the register-staged kernels, never the LDS-DMA ones | tolerance */                              \
+     conv_h3.hip, conv_wgrad_h3.hip: forward and weight gradient on the register-staged kernels, never the LDS-DMA ones | tolerance */           \
   X(WDNO_DBG_ROW_ATTN_AND_REG_STAGED_CONV, 5)                                                                                                      \
-  X(WDNO_DBG_WGRAD_NO_XCD_GROUPING, 6)  /* conv_h3.hip, conv_wgrad_h3d.hip: weight-gradient blocks / items in plain round-robin order | tolerance */ \
+  X(WDNO_DBG_WGRAD_NO_XCD_GROUPING, 6)  /* conv_wgrad_h3.hip, conv_wgrad_h3d.hip: weight-gradient blocks / items in plain round-robin order | tolerance */ \
   X(WDNO_DBG_FORCE_DMA_CONV, 7)         /* conv_h3.hip: forward always on the LDS-DMA kernels, whatever the tile count | tolerance */            \
   /* 8: conv_h3.hip as 7; conv_h3t.hip: never the tap-resident forward; conv_wgrad_h3d.hip: never the window weight gradients | tolerance */     \
   X(WDNO_DBG_CHUNKED_DMA_CONV, 8)                                                                                                                  \

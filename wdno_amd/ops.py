@@ -566,7 +566,7 @@ class _WPlan:
 
 
 def _wmode(kind):
-    """pack mode of csrc/conv_h3.hip: 'f' forward operand, 'd' data-gradient operand, 'p{py}{px}' parity class of a transposed convolution."""
+    """pack mode of csrc/conv_prep.hip: 'f' forward operand, 'd' data-gradient operand, 'p{py}{px}' parity class of a transposed convolution."""
     if kind[0] == 'q':              # tap (py, px) of a (1,2,2) / stride-2 convolution as the data-gradient operand of a 1x1 convolution
         return 6 + 2 * int(kind[1]) + int(kind[2])
     if kind[0] == 'a':              # 'aq' / 'ao': to_qkv / to_out of a temporal attention block in the fragment order of csrc/attn_fused_wide.hip
