@@ -257,7 +257,7 @@ def test_resident_tensor_loader_and_trainer_pick_it_up(trees, tmp_path):
 
 def test_pack_smoke_fields_equals_the_transform_then_pack_chain(trees):
     """wdno_pack_smoke_fields: fields + smoke-out curve -> states in two launches (3-D analysis + a packing launch that transforms the two condition
-    channels itself) against the chain it replaces -- offline-style transforms (3-D, 2-D of rho(t = 0), 1-D of the curve: csrc/dwt.hip, pinned to
+    channels itself) against the chain it replaces -- offline-style transforms (3-D, 2-D of rho(t = 0), 1-D of the curve: csrc/dwt.hip and the fused csrc/dwt_analysis.hip, pinned to
     PyWavelets by tests/test_gpu_ops.py) followed by the packing of data_2d.py:156-221. Coefficient channels are the same launches' bits; the condition
     channels agree to fp32 rounding (another order of the same fused multiply-adds)."""
     from ddpm.data_2d import pack_smoke_batch, pack_smoke_fields, _RESCALERS

@@ -1,4 +1,4 @@
-"""The fused single-launch DWT / IDWT kernels (csrc/dwt.hip, dwt_*_fused_kernel) against the per-axis kernels they replace.
+"""The fused single-launch DWT / IDWT kernels (csrc/dwt_analysis.hip, csrc/dwt_synthesis.hip) against the per-axis kernels of csrc/dwt.hip they replace.
 
 Both run the same pass order and the same fmaf chains, so the comparison is BIT-EXACT (torch.equal) for all four entry points
 (fwd, inv, inv_adjoint, fwd_adjoint), every embedded wavelet (L = 2 .. 10), both boundary modes, odd and ragged sizes, and padded
@@ -50,6 +50,10 @@ CASES = [
     (3, 'periodization', 'bior2.4', (2, 16, 20, 24)),
     (3, 'periodization', 'bior2.2', (2, 7, 9, 12)),
     (3, 'periodization', 'db3', (1, 8, 10, 6)),
+    # the smallest shapes that reach the kernels no case above launches (by the arithmetic of fused_synthesis, csrc/dwt_synthesis.hip)
+    (2, 'periodization', 'bior2.4', (1, 12, 300)),          # dwt_synthesis2_kernel<.., PMAX = 2>: staged rows of 128 < RW = 156 <= 256 floats
+    (2, 'zero', 'bior1.3', (1, 10, 520)),                   # dwt_synthesis_fused_kernel<2, ..>: RW = 262 > 256
+    (3, 'periodization', 'bior2.4', (1, 10, 12, 80)),       # dwt_synthesis3_stream_kernel<.., WMAX = 8>: n_w = 1120 > 1024 W-pass items per frame
 ]
 
 

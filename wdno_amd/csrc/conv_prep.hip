@@ -230,7 +230,7 @@ __host__ __device__ static inline PackTile pack_tile(int T, int A, int B, int mo
   t.tiles_c = (cext + t.CT - 1) / t.CT;
   return t;
 }
-// n / d for n * d < 2^32 with m = 2^32 / d + 1 (d > 1)
+// n / d for n * d < 2^32 with m = 2^32 / d + 1 (d > 1). Own copy of fastdiv.h's helper: on FastDiv both weight-pack kernels gain nine scalar instructions
 __device__ __forceinline__ unsigned ps_magic(unsigned d) { return d > 1 ? (unsigned)((1ull << 32) / d) + 1u : 0u; }
 __device__ __forceinline__ int ps_div(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
 __device__ __forceinline__ void pack_split_body(const float* __restrict__ w, const float* __restrict__ amax,

@@ -2,7 +2,7 @@
 //
 // One global integer, wdno_debug_mode (defined in api.cpp; set by wdno_set_debug() or, through the Python loader, by WDNO_DEBUG), steers
 // kernel selection for A/B measurements and for tests that pin a kernel. 0 in production. Host code reads it at launch (or graph capture)
-// time; the kernels that read it get it as a kernel argument (ConvP::debug from conv_common.h, the DWT geometry's `debug` from dwt.hip).
+// time; the kernels that read it get it as a kernel argument (ConvP::debug from conv_common.h, the DWT geometry's `debug` from dwt_tiles.h).
 // wdno_set_debug() refuses every value that is not listed here.
 //
 // One line per mode: value | files that read it | what it selects | results: "same bits" (bit-identical to mode 0), "tolerance" (another
@@ -23,9 +23,9 @@
   /* 11 is a list: dwt.hip: the per-axis passes instead of the fused transform (same bits); conv_wgrad_h3d.hip: the window weight gradient       \
      only for K <= 64 (tolerance) */                                                                                                             \
   X(WDNO_DBG_PER_AXIS_DWT_AND_WGRAD_WINDOW_K64, 11)                                                                                                \
-  X(WDNO_DBG_DWT_SKIP_W_PASS, 12)       /* dwt.hip, in the fused synthesis kernel: without the W pass | WRONG */                                 \
-  X(WDNO_DBG_DWT_SKIP_H_PASS, 13)       /* dwt.hip, same kernel (3-D): without the H pass | WRONG */                                             \
-  X(WDNO_DBG_DWT_SKIP_T_PASS, 14)       /* dwt.hip, same kernel (3-D): without the T pass and its stores | WRONG */                              \
+  X(WDNO_DBG_DWT_SKIP_W_PASS, 12)       /* dwt_synthesis.hip, in the fused synthesis kernel: without the W pass | WRONG */                      \
+  X(WDNO_DBG_DWT_SKIP_H_PASS, 13)       /* dwt_synthesis.hip, same kernel (3-D): without the H pass | WRONG */                                  \
+  X(WDNO_DBG_DWT_SKIP_T_PASS, 14)       /* dwt_synthesis.hip, same kernel (3-D): without the T pass and its stores | WRONG */                   \
   /* 21: conv_h3d.hip, conv_h3t.hip, conv_wgrad_h3d.hip, in the kernels: the DMA wave issues nothing, compute waves run on stale LDS | WRONG */   \
   X(WDNO_DBG_NO_DMA, 21)                                                                                                                           \
   X(WDNO_DBG_WGRAD_NO_DMA_NO_PIECE, 22) /* conv_wgrad_h3d.hip, in the kernel: as 21 and without the piece bookkeeping | WRONG */                 \
@@ -36,7 +36,7 @@
   X(WDNO_DBG_FORCE_TILES_160, 30)       /* conv_h3.hip as 7; conv_h3d.hip: tap-resident tiles 160 x 128 (320 x 64 for K <= 64) | tolerance */    \
   X(WDNO_DBG_FORCE_TILES_320, 31)       /* conv_h3.hip as 7; conv_h3d.hip: tap-resident tiles 320 x 64 | tolerance */                            \
   X(WDNO_DBG_ATTN_GENERIC_NTOK, 44)     /* attention.hip: the generic-length MFMA kernels at 24 tokens, not the <24> instantiation | tolerance */ \
-  X(WDNO_DBG_DWT3_SYNTH_LDS, 45)        /* dwt.hip: 3-D synthesis with all frames of a tile in LDS, not the streaming kernel | same bits */      \
+  X(WDNO_DBG_DWT3_SYNTH_LDS, 45)        /* dwt_synthesis.hip: 3-D synthesis with all frames of a tile in LDS, not the streaming kernel | same bits */      \
   X(WDNO_DBG_CONV_NO_RUN_SPLIT, 56)     /* conv_h3t.hip (read through conv_h3d.hip, conv_h3.hip): reductions never cut into four runs | tolerance */ \
   X(WDNO_DBG_STEM_EVERY_STAGE, 57)      /* conv_h3t.hip, in the kernel: the zero-box hint is ignored, every stage runs | same bits */            \
   X(WDNO_DBG_ATTN_FWD_ROWS, 67)         /* attention.hip: forward beyond 64 tokens on the thread-per-row kernel, not the tiled one | tolerance */ \

@@ -9,20 +9,16 @@
 // out (26.6 + 51.6 MB at the bench batch). The division is IEEE (what torch's `state / RESCALER` computes): results are bit-identical to the
 // torch formulation (tests/test_gpu_data.py).
 #include "common.h"
+#include "fastdiv.h"
 
 #define PK_MAXL 16
 #define PK_LB 6          // filters up to this length take the all-rows-in-flight form of the initial-density transform
-// n / d as one multiply-high for 0 <= n, n * d < 2^32 (csrc/dwt.hip: FastDiv): a hardware integer division is ~30 VALU instructions on gfx950, and
-// four of them per float4 made this kernel ALU-bound (33 us for 78 MB, profiles/r06_pack_kernel_stats.md)
-struct PkDiv { unsigned d, m; };
-static inline PkDiv pk_make_div(int d) { PkDiv f; f.d = (unsigned)d; f.m = d > 1 ? (unsigned)((1ull << 32) / (unsigned)d + 1ull) : 0u; return f; }
-__device__ __forceinline__ unsigned pk_div(unsigned n, PkDiv f) { return f.d == 1 ? n : __umulhi(n, f.m); }
 
 struct PackSmokeP {
   const float* coef; const float* init; const float* so; const int64_t* idx; const float* resc; float* out;
   int64_t coef_sim, init_sim, so_sim;      // elements between consecutive simulations in the three stores
   int F, nt, nx, pad_t, pad_x, C;
-  PkDiv dW4, dPX;
+  FastDiv dW4, dPX;          // (fastdiv.h: four hardware divisions per float4 made the kernel ALU-bound)
   // FIELDS form: the two condition channels transformed in place from the physical fields (zero-mode analysis):
   // init = rho(t = 0) [.][H0][W0], so = the smoke-out curve [.][T0]; flo / fhi = the FLIPPED decomposition filters (flo[m] = dec_lo[L - 1 - m])
   int L, H0, W0, T0;
@@ -59,9 +55,9 @@ __global__ __launch_bounds__(256) void pack_smoke_state_kernel(PackSmokeP p) {
   const int64_t sim = p.idx ? p.idx[b] : b;
   float4* __restrict__ out = reinterpret_cast<float4*>(p.out) + (size_t)blockIdx.x * fstride4;
   for (unsigned i = blockIdx.y * 256u + threadIdx.x; i < fstride4; i += stride) {
-    unsigned q = pk_div(i, p.dW4);
+    unsigned q = fd_div(i, p.dW4);
     const int w0 = (int)(i - q * W4) * 4;
-    const unsigned cc = pk_div(q, p.dPX);
+    const unsigned cc = fd_div(q, p.dPX);
     const int h = (int)(q - cc * (unsigned)p.pad_x), c = (int)cc;
     const float r = p.resc[c];
     float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -160,13 +156,13 @@ static inline dim3 pk_grid(int64_t B, int pad_t, int C, int pad_x) {
 static inline int pk_check(int64_t B, int pad_t, int pad_x, int C) {
   if ((pad_x & 3) || (pad_t & 3)) return WDNO_EUNSUPPORTED;            // four sub-bands over pad_t frames; 16-byte rows
   if (B * pad_t >= (1ll << 31) || (int64_t)C * pad_x * (pad_x >> 2) * pad_x >= (1ll << 31) || (int64_t)C * pad_x * (pad_x >> 2) > 65535ll * 256 * 8)
-    return WDNO_EUNSUPPORTED;           // grid; pk_div range
+    return WDNO_EUNSUPPORTED;           // grid; fd_div range
   return WDNO_OK;
 }
 
 static void pk_common(PackSmokeP& p, int64_t B, int F, int nt, int nx, int pad_t, int pad_x) {
   p.F = F; p.nt = nt; p.nx = nx; p.pad_t = pad_t; p.pad_x = pad_x; p.C = 8 * F + 2;
-  p.dW4 = pk_make_div(pad_x >> 2); p.dPX = pk_make_div(pad_x);
+  p.dW4 = make_fastdiv(pad_x >> 2); p.dPX = make_fastdiv(pad_x);
   p.L = 0; p.H0 = p.W0 = p.T0 = 0;
 }
 

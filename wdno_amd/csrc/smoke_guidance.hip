@@ -3,7 +3,7 @@
 // (launch 1) -- adjoint synthesis, schedule, add, and the copy of everything J does not reach (launch 2). include/wdno_hip.h states the
 // mathematics; wdno_amd/smoke/guidance.py: plan() chooses the tiles.
 //
-// Zero-mode filter bank of L = 6 taps (bior1.3), off = L - 2 = 4, one axis (csrc/dwt.hip: synthesis_kernel / analysis_kernel with reversed taps):
+// Zero-mode filter bank of L = 6 taps (bior1.3), off = L - 2 = 4, one axis (csrc/dwt.hip: the per-axis synthesis_kernel / analysis_kernel with reversed taps):
 //   synthesis  x[n]  = sum over m < L with n + 4 - m even, K = (n + 4 - m) / 2 in [0, M):  lo[K] g_lo[m] + hi[K] g_hi[m]        (N = 2M - 4)
 //   adjoint    dlo[K] = sum over m < L with n = 2K + m - 4 in [0, N):  g_lo[m] r[n],   dhi likewise
 // in the order W, H, T (synthesis) and T, H, W (adjoint) with band = 4 bt + 2 bh + bw, the channel of field f being 8 f + band.
