@@ -862,6 +862,50 @@ typedef struct {
 } wdno_smoke_score_channel;
 int wdno_smoke_score(const float* pred, const wdno_smoke_score_channel* data, double* out, int B, int T, int h, int w, wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ smoke inference: the super-resolution cascade
+ * wdno_smoke_reconstruct_at: wdno_smoke_reconstruct with the coefficient block read at rows and columns off .. off + hc / wc of the tensor
+ * (tensor_to_coef(..., upsample_type='space') of smoke/inference_2d.py:219 is off = 1; hc + off <= H, wc + off <= W). The smoke-out means
+ * still run over the whole rows < half and >= half of channel C - 1: the offset moves the coefficient block only. off = 0 is
+ * wdno_smoke_reconstruct bit for bit. */
+int wdno_smoke_reconstruct_at(const float* x, const float* rescaler, float* pred, const wdno_smoke_reconstruct_desc* d, int off,
+                              const float* filt, wdno_stream_t s);
+
+/* wdno_smoke_cascade_conditions: what run_super_model (smoke/inference_2d.py:176-196) hands to the super model's sample() as low,
+ * init / RESCALER[-2] and control / RESCALER[24:40], written in one launch as the sampler's condition source
+ * src [B][pad_t][82][pad_x][pad_x] (fp32, 16-byte aligned, network units; every element is written):
+ *   src[b, f, 40 + c, h, w] = prev[b, f, c, h / 2, w / 2]                      f < t0, h < 2 h0, w < 2 w0, c < 40; 0 beyond. Copied, not rescaled.
+ *   src[b, f, 24 + 8 g + band, h, w] = coef[b, g, band, f, clamp(h - 1), clamp(w - 1)] / rescaler[24 + 8 g + band]
+ *                                                                             f < t1, h < h1 + 2, w < w1 + 2; 0 / rescaler beyond
+ *   src[b, f, 80, h, w] = DWT2(rho0[b])[f % 4][h, w] / rescaler[80]           h < h1, w < w1; 0 / rescaler beyond
+ *   every other channel = 0
+ * prev: the base level's sample [B][F0][C0 >= 40][H0][W0] with element strides (columns contiguous); coef: the packed zero-mode 3-D analysis
+ * [B][2][8][t1][h1][w1] of the fine controls, contiguous; rho0: the fine initial density [B][Hf][Wf] with sample and row strides; DWT2 is the
+ * zero-mode analysis with sub-bands in the order Yl, Yh[0][:, 0]'s three, and the frame order f % 4 is the reference's at this level (l.181),
+ * not the base level's. rescaler [82]; filt as for wdno_smoke_guidance. Requires 2 h0 == h1 + 2, 2 w0 == w1 + 2, h1 + 2 <= pad_x,
+ * w1 + 2 <= pad_x, h1 == (Hf + L - 1) / 2, w1 == (Wf + L - 1) / 2, pad_t % 4 == 0, pad_x % 4 == 0, sample strides < 2^31: WDNO_EINVAL otherwise;
+ * WDNO_EUNSUPPORTED for anything but mode 1 (zero), L = 6 (bior1.3), C = 82. Nothing is allocated. */
+typedef struct {
+  long long prev_sample_stride, rho_sample_stride;
+  int prev_frame_stride, prev_chan_stride, prev_row_stride, rho_row_stride;
+  int B, F0, C0, H0, W0;
+  int t0, h0, w0, t1, h1, w1, Hf, Wf;
+  int pad_t, pad_x, C, L, mode;
+} wdno_smoke_cascade_desc;
+int wdno_smoke_cascade_conditions(const float* prev, const float* coef, const float* rho0, const float* rescaler, float* src,
+                                  const wdno_smoke_cascade_desc* d, const float* filt, wdno_stream_t s);
+
+/* wdno_smoke_score_super: the sums of the four comparisons of InferencePipeline.multi_evaluate's super-resolution branch in simulation mode
+ * (smoke/inference_2d.py:405-439) in one launch, a workgroup per (sample, comparison). pred [B][T][6][n][n] fp32, contiguous; data: six
+ * channel entries as for wdno_smoke_score, describing the data at its FULL resolution N x N; n == N or 2 n == N, N even. out [B][4][5] fp64,
+ * the five sums of wdno_smoke_score per comparison, over the comparison's own grid:
+ *   0 base     pred at stride 2 n / N   against data at stride 2          (N / 2 cells a side)
+ *   1 current  pred                     against data at stride N / n      (n cells a side)
+ *   2 linear   pred interpolated bilinearly (align_corners = False) to N cells a side, against data
+ *   3 nearest  pred[h n / N, w n / N] against data
+ * The interpolated tensors are never built: for N == 2 n the bilinear value is formed in fp64 from the four neighbours with the weights
+ * 0.25 / 0.75 and the edge clamp of F.interpolate; for N == n comparisons 2 and 3 read pred itself. */
+int wdno_smoke_score_super(const float* pred, const wdno_smoke_score_channel* data, double* out, int B, int T, int n, int N, wdno_stream_t s);
+
 /* ------------------------------------------------------------------------------------------------ Burgers evaluation: reconstruction and scoring
  * wdno_burgers_reconstruct: the wavelet branch of diffuse_2dconv (eval_ddpm_burgers.py:185-195) for the whole batch in one launch. For the
  * sampled state x [B][C][H][W] in network units (C >= 8, strides in elements, columns contiguous), rescaler [>= 8], the coefficient block

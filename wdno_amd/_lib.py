@@ -113,6 +113,12 @@ class SmokeScoreChannel(C.Structure):       # include/wdno_hip.h: wdno_smoke_sco
                [('is_double', I), ('reserved', I)]
 
 
+class SmokeCascadeDesc(C.Structure):        # include/wdno_hip.h: wdno_smoke_cascade_desc
+    _fields_ = [(k, C.c_longlong) for k in ('prev_sample_stride', 'rho_sample_stride')] + \
+               [(k, I) for k in ('prev_frame_stride', 'prev_chan_stride', 'prev_row_stride', 'rho_row_stride', 'B', 'F0', 'C0', 'H0', 'W0', 't0', 'h0',
+                                 'w0', 't1', 'h1', 'w1', 'Hf', 'Wf', 'pad_t', 'pad_x', 'C', 'L', 'mode')]
+
+
 class BurgersReconstructDesc(C.Structure):  # include/wdno_hip.h: wdno_burgers_reconstruct_desc
     _fields_ = [(k, I) for k in ('B', 'C', 'H', 'W')] + [('sample_stride', C.c_longlong)] + \
                [(k, I) for k in ('chan_stride', 'row_stride', 'h', 'w', 'n_t', 'n_x', 'L', 'mode', 'tn', 'ntile', 'lds_bytes', 'reserved')]
@@ -272,6 +278,9 @@ PROTOTYPES = {
     'wdno_smoke_noise': (I, [P, P, P, P, I, C.c_uint64, P, P]),
     'wdno_smoke_reconstruct': (I, [P, P, P, C.POINTER(SmokeReconstructDesc), PF, P]),
     'wdno_smoke_score': (I, [P, C.POINTER(SmokeScoreChannel), P, I, I, I, I, P]),
+    'wdno_smoke_reconstruct_at': (I, [P, P, P, C.POINTER(SmokeReconstructDesc), I, PF, P]),
+    'wdno_smoke_cascade_conditions': (I, [P, P, P, P, P, C.POINTER(SmokeCascadeDesc), PF, P]),
+    'wdno_smoke_score_super': (I, [P, C.POINTER(SmokeScoreChannel), P, I, I, I, I, P]),
     'wdno_burgers_reconstruct': (I, [P, P, P, P, C.POINTER(BurgersReconstructDesc), PF, P]),
     'wdno_burgers_score': (I, [P, P, P, P, P, C.POINTER(BurgersScoreDesc), P]),
 }

@@ -19,6 +19,8 @@
 // the reference forms it) over rows < half and rows >= half of the tn / 2 + 2 coefficient frames its frames read -- per-thread strided sums,
 // then a tree over the 256 threads --, rounds the means to fp32, synthesises its tn frames and stores each value to the ho wo cells.
 // Nothing is atomic and every sum has a fixed order: a sample's bits do not depend on the batch size or on its index.
+// wdno_smoke_reconstruct_at: the coefficient block starts at row and column `off` of the tensor (the space super-resolution level,
+// smoke/inference_2d.py:219: off = 1); the smoke-out blocks do not move.
 #include "common.h"
 #include "idx3.h"
 
@@ -36,6 +38,7 @@ struct SRecP {
   int tc, hc, wc, to, ho, wo;
   int half, tn, hn;
   int ntiles;                                // tile blocks per sample; the blocks after them are smoke-out blocks
+  int off;                                   // row and column at which the coefficient block starts (wdno_smoke_reconstruct_at)
 };
 
 __device__ __forceinline__ void tile_block(const SRecP& p, const RTaps& g, float* smem, int blk, int b) {
@@ -47,7 +50,7 @@ __device__ __forceinline__ void tile_block(const SRecP& p, const RTaps& g, float
   const int n0 = (blk / nrt) * tn, h0 = (blk % nrt) * hn, k0h = h0 / 2;
   float* const A1 = smem;                         // [4][tn][KH][wc]
   float* const A2 = A1 + 4 * tn * KH * wc;        // [2][tn][hn][wc]
-  const float* const xb = p.x + (size_t)b * p.ss;
+  const float* const xb = p.x + (size_t)b * p.ss + (size_t)p.off * p.rs + p.off;      // the block's first row and column
   // T pass
   for (int q = 0; q < 4; ++q) {
     const int ch = 8 * field + q;
@@ -181,21 +184,27 @@ int validate(const wdno_smoke_reconstruct_desc* d) {
 
 }  // namespace
 
-extern "C" int wdno_smoke_reconstruct(const float* x, const float* rescaler, float* pred, const wdno_smoke_reconstruct_desc* d, const float* filt,
-                                      wdno_stream_t s) {
+extern "C" int wdno_smoke_reconstruct_at(const float* x, const float* rescaler, float* pred, const wdno_smoke_reconstruct_desc* d, int off,
+                                         const float* filt, wdno_stream_t s) {
   WDNO_REQUIRE(x && rescaler && pred && d && filt && x != pred);
   const int rc = validate(d);
   if (rc) return rc;
+  WDNO_REQUIRE(off >= 0 && d->hc + off <= d->H && d->wc + off <= d->W);
   SRecP p;
   p.x = x; p.resc = rescaler; p.pred = pred;
   p.F = d->F; p.C = d->C; p.H = d->H; p.W = d->W;
   p.ss = d->sample_stride; p.fs = d->frame_stride; p.cs = d->chan_stride; p.rs = d->row_stride;
   p.tc = d->tc; p.hc = d->hc; p.wc = d->wc; p.to = d->to; p.ho = d->ho; p.wo = d->wo;
-  p.half = d->half; p.tn = d->tn; p.hn = d->hn;
+  p.half = d->half; p.tn = d->tn; p.hn = d->hn; p.off = off;
   const int nft = cdiv(d->to, d->tn);
   p.ntiles = 5 * nft * cdiv(d->ho, d->hn);
   RTaps g;
   for (int m = 0; m < L; ++m) { g.lo[m] = filt[2 * L + m]; g.hi[m] = filt[3 * L + m]; }
   smoke_reconstruct_kernel<<<dim3(p.ntiles + nft, d->B), NT, (size_t)d->lds_bytes, as_stream(s)>>>(p, g);
   return wdno_check_launch();
+}
+
+extern "C" int wdno_smoke_reconstruct(const float* x, const float* rescaler, float* pred, const wdno_smoke_reconstruct_desc* d, const float* filt,
+                                      wdno_stream_t s) {
+  return wdno_smoke_reconstruct_at(x, rescaler, pred, d, 0, filt, s);
 }

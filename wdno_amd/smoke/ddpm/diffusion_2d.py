@@ -253,8 +253,28 @@ class GaussianDiffusion(nn.Module):
         return K.sampling_loop(self, x, src, desc, cond_first=False, use_graph=self.use_graph, guidance=design_fn,
                                s_table=self.guidance_s_table(design_guidance), guidance_key=gkey, **kw)
 
+    _cond_src = None
+
+    def sample_with_source(self, cond_src, **kwargs):
+        """sample(**kwargs) with the condition source handed over assembled (an extension; sample, p_sample_loop and ddim_sample keep the
+        reference's parameter lists): cond_src is a contiguous fp32 tensor of the sampled shape on the sampling device whose conditioned
+        positions hold the clean values (smoke/cascade.py: super_conditions). It is used as it is instead of a zeroed tensor and three
+        copies; init, control and low are still passed, as views of it, for the shapes and for a design_fn that reads them."""
+        self._cond_src = cond_src
+        try:
+            return self.sample(**kwargs)
+        finally:
+            self._cond_src = None
+
     def _condition_source(self, shape, device, init, control, low):
-        """Clean values for every conditioned position, assembled once per sampling call."""
+        """Clean values for every conditioned position, assembled once per sampling call (or handed over by sample_with_source)."""
+        cond_src = self._cond_src
+        if cond_src is not None:
+            if tuple(cond_src.shape) != tuple(shape) or cond_src.dtype != torch.float32 or cond_src.device != torch.device(device) or \
+                    not cond_src.is_contiguous():
+                raise ValueError(f'cond_src must be a contiguous float32 {tuple(shape)} tensor on {device}, got {cond_src.dtype} '
+                                 f'{tuple(cond_src.shape)} on {cond_src.device}')
+            return cond_src
         src = torch.zeros(shape, device=device, dtype=torch.float32)
         assert init is not None
         src[:, :, -2] = init.to(device)

@@ -286,6 +286,69 @@ class SmokeGuidance:
         return self._launch(_chk(x_t, 'x_t'), eps, t, mod.sqrt_recip_alphas_cumprod, mod.sqrt_recipm1_alphas_cumprod, s_table, clip_x0, self.init_u)
 
 
+class CascadeGuidance:
+    """`design_fn` of the super-resolution cascade (load_model's closure, smoke/inference_2d.py:81-91): one SmokeGuidance per level -- level 0
+    on the base model's 42-channel RESCALER, level i on the super model's 82-channel one with shape[i], ori_shape[i] -- behind the interface
+    the sampler uses (fused_step, graph_safe, set_init_u, guide, key, __call__), so every level keeps the captured guided step.
+
+    The reference dispatches on `low is None`; a level's tensor has its RESCALER's channel count, and its initial density its field size, so
+    the object dispatches on the tensor it is given. At a super level the reference's guidance_fn calls tensor_to_coef without upsample_type
+    and therefore reads the coefficient block at offset 0 of the tensor whose block sits at offset 1, and splits the smoke-out rows at
+    int(40 / 2); SmokeGuidance does both already, and this object leaves it so."""
+
+    def __init__(self, levels):
+        self.levels = list(levels)
+        chans = [int(g.rescaler.numel()) for g in self.levels]
+        fields = [g.ori_shape[1:] for g in self.levels]
+        if len(set(chans)) != len(chans) and len(set(fields)) != len(fields):
+            raise ValueError(f'CascadeGuidance: levels with channels {chans} and fields {fields} cannot be told apart')
+        self._active = None
+
+    @property
+    def fused_step(self):
+        return all(g.fused_step for g in self.levels)
+
+    @property
+    def graph_safe(self):
+        return all(g.graph_safe for g in self.levels)
+
+    def level_of(self, x):
+        """The level whose tensor x [B, F, C, H, W] is: by channel count, then by the initial density's field size set last."""
+        hits = [g for g in self.levels if int(g.rescaler.numel()) == int(x.shape[2])]
+        if len(hits) == 1:
+            return hits[0]
+        if self._active is not None and self._active in hits:
+            return self._active
+        raise ValueError(f'CascadeGuidance: no single level takes a tensor of {tuple(x.shape)}')
+
+    def set_init_u(self, init_u, device=None):
+        if init_u is None:
+            for g in self.levels:
+                g.set_init_u(None)
+            self._active = None
+            return self
+        hw = tuple(int(v) for v in init_u.shape[-2:])
+        hits = [g for g in self.levels if tuple(g.ori_shape[1:]) == hw]
+        if len(hits) != 1:
+            raise ValueError(f'CascadeGuidance: an initial density of {hw} cells belongs to {len(hits)} of the levels {[g.ori_shape for g in self.levels]}')
+        self._active = hits[0]
+        hits[0].set_init_u(init_u, device)
+        return self
+
+    def key(self):
+        """The key of the level whose initial density was set last (the sampler sets it right before it builds the step's key), so one
+        level's captured step does not depend on the other level's buffers."""
+        if self._active is None:
+            return tuple(g.key() for g in self.levels)
+        return (self.levels.index(self._active), self._active.key())
+
+    def guide(self, mod, x_t, eps, t, s_table, clip_x0):
+        return self.level_of(eps).guide(mod, x_t, eps, t, s_table, clip_x0)
+
+    def __call__(self, x, low=None, init=None, init_u=None):
+        return self.level_of(x)(x, low=low, init=init, init_u=init_u)
+
+
 class GuidanceFn:
     """`design_fn` for GaussianDiffusion.sample (called as design_fn(x, low=, init=, init_u=), inference_2d.py:30-66) on the explicit
     gradient. `graph_safe = True` tells the sampler that the callback launches only capturable work."""

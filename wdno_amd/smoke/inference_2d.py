@@ -14,8 +14,21 @@ tree ahead of the reference on sys.path, `python inference_2d.py --is_wavelet Tr
                           metrics read; csrc/smoke_score.hip reads them in place) or score (simulation mode)
   run / save_results      the reference's results.txt / results_sim.txt lines
 
-Out of scope, raising NotImplementedError with the reference's line: is_wavelet=False (inference_2d.py:133-136), is_super_model=True and
-run_super_model (inference_2d.py:155-232; the cascade has its own route, tests/test_gpu_super.py), plot=True (inference_2d.py:372-378).
+and, with `--is_super_model True --upsample 1 --is_condition_control True`, the zero-shot space super-resolution cascade (a model list of two):
+
+  load_model              the base model on RESCALER[:, :, 40:], the super model on RESCALER; design_fn = wdno_amd.smoke.guidance.CascadeGuidance,
+                          a SmokeGuidance per level, so both levels keep the fused, graph-replayed guided step
+  run_super_model         sample() of the base model; wdno_amd.smoke.cascade.super_conditions: low, init and control of the super level as the
+                          sampler's condition source in two launches (csrc/smoke_cascade.hip), handed over by sample_with_source; sample() of
+                          the super model; reconstruct() per level, the super level's block at offset 1 and its smoke-out rows split at 40
+  multi_evaluate          per level the reference's four comparisons (base / current / linear / nearest) from one launch
+                          (wdno_amd.smoke.score.score_super), mse_wo_smoke in the mse slot as in the reference (l.447-448)
+  run                     scores every level into J_totals[i] ... n_l2s[i]
+
+Out of scope, raising NotImplementedError with the reference's line: is_wavelet=False (inference_2d.py:133-136); is_super_model=True with
+upsample=0 (a cascade without a super level is the base driver), a two-model list without is_super_model and run_super_model on a
+one-model pipeline (inference_2d.py:155-232); upsample >= 2 (inference_2d.py:177: the slice step 2 ** (1 - i) is fractional there);
+is_super_model=True with is_condition_control=False (inference_2d.py:157: the reference asserts it); plot=True (inference_2d.py:372-378).
 Anything else falls through to the reference's module when that is on sys.path behind this tree."""
 import argparse
 import datetime
@@ -45,13 +58,32 @@ def guidance_fn(x, args, shape, ori_shape, RESCALER, w_energy=0, w_init=0, low=N
                                   w_init, init_u)
 
 
+def _check_cascade(args, line):
+    """The one cascade the reference can run: upsample=1 in simulation mode."""
+    up = int(getattr(args, 'upsample', 0))
+    if up == 0:
+        _unsupported('is_super_model=True with upsample=0 (a cascade without a super level is the base driver)', line)
+    if up >= 2:
+        _unsupported(f'upsample={up} (the reference slices the fields with the step 2 ** (1 - i), fractional for i >= 2; its data is 2x the base grid)', '177')
+    if not args.is_condition_control:
+        _unsupported('is_super_model=True with is_condition_control=False (the reference asserts is_condition_control)', '157')
+
+
 def load_model(args, shape, ori_shape, RESCALER):
-    if args.is_super_model:
-        _unsupported('is_super_model=True', '72-75')
     if not args.is_wavelet:
         _unsupported('is_wavelet=False', '56-63')
+    from wdno_amd.smoke.guidance import CascadeGuidance, SmokeGuidance
+    if args.is_super_model:
+        _check_cascade(args, '72-75')
+        from ddpm.utils import load_ddpm_base_model, load_ddpm_super_model      # the reference's loaders, on this tree's model classes
+        diffusion, device = load_ddpm_base_model(args, shape[0], ori_shape[0], RESCALER[:, :, 40:])
+        diffusion_super, device = load_ddpm_super_model(args, shape, ori_shape, RESCALER)
+        kw = dict(is_condition_control=args.is_condition_control, w_energy=args.w_energy, w_init=args.w_init, wave_type=args.wave_type,
+                  pad_mode=args.pad_mode)
+        levels = [SmokeGuidance(shape[0], ori_shape[0], RESCALER[:, :, 40:], **kw)]
+        levels += [SmokeGuidance(shape[i], ori_shape[i], RESCALER, **kw) for i in range(1, int(args.upsample) + 1)]
+        return [diffusion, diffusion_super], CascadeGuidance(levels)
     from ddpm.utils import load_ddpm_base_model          # the reference's loader (falls through ddpm/__init__.py), on this tree's model classes
-    from wdno_amd.smoke.guidance import SmokeGuidance
     diffusion, device = load_ddpm_base_model(args, shape, ori_shape, RESCALER)
     design_fn = SmokeGuidance(shape, ori_shape, RESCALER, is_condition_control=args.is_condition_control, w_energy=args.w_energy,
                               w_init=args.w_init, wave_type=args.wave_type, pad_mode=args.pad_mode)
@@ -73,8 +105,11 @@ class InferencePipeline(object):
         self.RESCALER = RESCALER
         if not self.is_wavelet:
             _unsupported('is_wavelet=False', '133-136')
-        if getattr(args_general, 'is_super_model', False) or len(model) != 1:
-            _unsupported('is_super_model=True', '155-232')
+        self.is_super_model = bool(getattr(args_general, 'is_super_model', False))
+        if self.is_super_model:
+            _check_cascade(args_general, '155-232')
+        if len(model) != (2 if self.is_super_model else 1):
+            _unsupported(f'a list of {len(model)} models with is_super_model={self.is_super_model}', '155-232')
         if not os.path.exists(self.results_path):
             os.makedirs(self.results_path)
 
@@ -93,7 +128,32 @@ class InferencePipeline(object):
         return reconstruct(output, m.padded_shape, m.ori_shape, self.RESCALER, m.wave_type, m.pad_mode)
 
     def run_super_model(self, state, state_ori, wave_init, wave_control):
-        _unsupported('run_super_model', '155-232')
+        """The reference's contract: state [B, to, 6, ho, wo] the base-resolution state, state_ori [B, to, 6, 2 ho, 2 wo] the batch as loaded,
+        wave_init / wave_control the base level's conditions NOT yet divided by RESCALER. Returns [pred_0, pred_1]."""
+        if len(self.model) != 2:
+            _unsupported('run_super_model on a one-model pipeline', '155-232')
+        r = torch.as_tensor(self.RESCALER).to(wave_init.device)
+        return self._cascade(state, state_ori, wave_init / r[:, :, -2], wave_control / r[:, :, 24:40])
+
+    def _cascade(self, state, state_ori, init, control):
+        """Base sample, the super level's conditions (network units throughout), super sample, one reconstruction per level."""
+        from wdno_amd.smoke.cascade import super_conditions, views
+        from wdno_amd.smoke.reconstruct import level_rescaler, reconstruct
+        m0, m1 = self.model
+        shape, ori_shape = m1.padded_shape, m1.ori_shape
+        kw = dict(batch_size=state.shape[0], design_fn=self.args['design_fn'], design_guidance=self.args['design_guidance'])
+        out0 = m0.sample(low=None, init=init, init_u=state[:, 0, 0], control=control, **kw)
+        fine = state_ori.to(out0.device, torch.float32)          # level 1 of simulation mode: the batch at stride 2 ** (1 - 1) (l.177)
+        pad_t, pad_x = int(getattr(m0, 'frames', PAD_T)), 2 * int(getattr(m0, 'image_size', PAD_X))
+        src = super_conditions(out0, shape[0], fine, self.RESCALER, shape[1], pad_t, pad_x, m1.wave_type, m1.pad_mode)
+        low, init1, control1 = views(src)
+        kw1 = dict(N_upsample=1, low=low, init=init1, init_u=fine[:, 0, 0], control=control1, **kw)
+        out1 = m1.sample_with_source(src, **kw1) if hasattr(m1, 'sample_with_source') else m1.sample(**kw1)
+        preds = []
+        for i, out in enumerate((out0, out1)):                    # l.213-231: both levels on the super model's RESCALER, rows split at int(H / 2)
+            preds.append(reconstruct(out, shape[i], ori_shape[i], level_rescaler(self.RESCALER, out.shape[2]), m0.wave_type, m0.pad_mode,
+                                     upsample_type='space' if i else None, half=int(out.shape[-2] / 2)))
+        return preds
 
     def run_model(self, state):
         """state: not rescaled, [B, 256, 6, nx, nx] (control) or [B, nt, 6, 2 nx, 2 nx] (simulation)."""
@@ -104,8 +164,11 @@ class InferencePipeline(object):
         fields = state[:, :, :5].permute(0, 2, 1, 3, 4).contiguous()
         curve = torch.zeros(fields.shape[0], fields.shape[2], device=fields.device, dtype=torch.float32)
         m = self.model[0]               # the sampler's tensor: 24 frames of 40 x 40 in the reference, whatever the model says it is here
-        packed = pack_smoke_fields(fields, curve, self.RESCALER, wave=m.wave_type, pad_t=int(getattr(m, 'frames', PAD_T)),
+        resc = torch.as_tensor(self.RESCALER).reshape(-1)[-42:]      # the base level's 42 entries (RESCALER[:, :, 40:] of a super model's 82)
+        packed = pack_smoke_fields(fields, curve, resc, wave=m.wave_type, pad_t=int(getattr(m, 'frames', PAD_T)),
                                    pad_x=int(getattr(m, 'image_size', PAD_X)))
+        if len(self.model) == 2:
+            return self._cascade(state, state_ori, packed[:, :, -2].contiguous(), packed[:, :, 24:40].contiguous())
         return self._sample_and_reconstruct(state, packed[:, :, -2].contiguous(), packed[:, :, 24:40].contiguous())
 
     def run(self, dataloader):
@@ -118,12 +181,15 @@ class InferencePipeline(object):
             state, shape, ori_shape, sim_id = data
             pred = self.run_model(state)
             preds.append(pred)
-            J_total, J_target, J_energy, mse, n_l2 = self.multi_evaluate(pred, state, plot=False)
-            J_totals[0].append(J_total)
-            J_targets[0].append(J_target)
-            J_energys[0].append(J_energy)
-            mses[0].append(mse)
-            n_l2s[0].append(n_l2)
+            for lvl, p in enumerate(pred if self.is_super_model else [pred]):
+                if self.is_super_model:
+                    print('Number of upsampling times:', lvl)
+                J_total, J_target, J_energy, mse, n_l2 = self.multi_evaluate(p, state, plot=False)
+                J_totals[lvl].append(J_total)
+                J_targets[lvl].append(J_target)
+                J_energys[lvl].append(J_energy)
+                mses[lvl].append(mse)
+                n_l2s[lvl].append(n_l2)
         print("Final results!")
         for i in range(self.upsample + 1):
             print(f"Number of upsampling times: {i}")
@@ -164,13 +230,29 @@ class InferencePipeline(object):
 
     def multi_evaluate(self, pred, data, plot=False):
         """pred [B, nt, 6, nx, nx]; data: control [B, 256, 6, nx, nx], simulation [B, nt, 6, 128, 128]. Returns the reference's five arrays of
-        one entry: J_total, J_target, J_energy, mse, n_l2 (batch means). As in the reference, pred[:, 0, 0] is overwritten with the data's."""
+        one entry: J_total, J_target, J_energy, mse, n_l2 (batch means). As in the reference, pred[:, 0, 0] is overwritten with the data's.
+        With is_super_model (simulation mode, inference_2d.py:405-456) pred is one level of the cascade and the five arrays have four entries:
+        base, current, linear and nearest super resolution, with mse_wo_smoke in the mse slot (l.447-448)."""
         from wdno_amd.smoke import score as S
         if plot:
             _unsupported('plot=True', '372-378')
         sp = int(data.shape[-1] / pred.shape[-1])
         pred[:, 0, 0] = data[:, 0, 0, ::sp, ::sp].to(pred.device, pred.dtype)      # initial condition
         w = self.args_general.w_energy
+        if getattr(self.args_general, 'is_super_model', False):
+            if not self.args_general.is_condition_control:
+                _unsupported('is_super_model=True with is_condition_control=False', '157')
+            d = data.to(pred.device)
+            if d.dtype not in (torch.float32, torch.float64):
+                d = d.to(torch.float32)
+            r = S.score_super(pred.to(torch.float32), d, w)
+            T, n, N = pred.shape[1], pred.shape[3], d.shape[-1]
+            print('current resolution:', T, n, n)
+            for i, (msg, g) in enumerate(zip(('base resolution', 'current resolution', 'linear super resolution', 'nearest super resolution'),
+                                             (N // 2, n, N, N))):
+                print(msg, ', evaluate shape:', T, g, g)
+                print('mse =', r['mse'][i].mean(), 'mse_wo_smoke =', r['mse_wo_smoke'][i].mean(), 'normalized_l2 =', r['n_l2'][i].mean())
+            return tuple(r[k].mean(1) for k in ('J_total', 'J_target', 'J_energy', 'mse_wo_smoke', 'n_l2'))
         if not self.args_general.is_condition_control:
             start = time.time()
             r = S.score_controls(pred, data, w)

@@ -10,6 +10,9 @@ ratio [B, 256] is read at frame stride 256 // T with zero spatial strides.
 
 score()          -- the launch and the metric formulas on its five fp64 sums per sample.
 score_controls() -- control mode: the indirect-control copy of pred, the frames-only solve, score().
+score_super()    -- simulation mode of a cascade level (smoke/inference_2d.py:405-456): the four comparisons base / current / linear / nearest
+                    from one launch (wdno_smoke_score_super). The reference interpolates pred to two [B, T, 6, 128, 128] tensors, masks eight
+                    tensors and reduces each four times; here the kernel samples pred through the interpolation while it reads the data in place.
 """
 import ctypes as C
 
@@ -55,6 +58,39 @@ def score(pred, data_channels, w_energy):
     j_target, j_energy = -s[:, 4], s[:, 3] / (2 * cells)
     return dict(mse=(s[:, 0] + s[:, 1]) / (4 * cells), mse_wo_smoke=s[:, 0] / (3 * cells), n_l2=np.sqrt(s[:, 0]) / np.sqrt(s[:, 2]),
                 J_target=j_target, J_energy=j_energy, J_total=j_target + w_energy * j_energy)
+
+
+def _metrics(s, cells, w_energy):
+    """KEYS from the five sums [..., 5] over `cells` cells per channel."""
+    j_target, j_energy = -s[..., 4], s[..., 3] / (2 * cells)
+    return dict(mse=(s[..., 0] + s[..., 1]) / (4 * cells), mse_wo_smoke=s[..., 0] / (3 * cells), n_l2=np.sqrt(s[..., 0]) / np.sqrt(s[..., 2]),
+                J_target=j_target, J_energy=j_energy, J_total=j_target + w_energy * j_energy)
+
+
+COMPARISONS = ('base', 'current', 'linear', 'nearest')
+
+
+def score_super(pred, data, w_energy):
+    """pred [B, T, 6, n, n] fp32 on the GPU (a cascade level), data [B, T, 6, N, N] fp32 or fp64 on pred's device (any strides), n == N or
+    2 n == N. Returns {key: fp64 numpy [4, B]} for KEYS: row i is COMPARISONS[i] of multi_evaluate's super-resolution branch --
+    base: pred at stride 2 n / N against data[..., ::2, ::2]; current: pred against data at stride N / n; linear / nearest: pred
+    interpolated (bilinear with align_corners=False / nearest) to N x N against data. The reference's 64 is N / 2 here."""
+    from wdno_amd import _lib
+    from wdno_amd.ops import _p, _stream
+    if not pred.is_cuda or pred.dtype != torch.float32 or pred.dim() != 5 or pred.shape[2] != 6 or pred.shape[3] != pred.shape[4]:
+        raise RuntimeError(f'smoke score: pred must be a float32 [B, T, 6, n, n] tensor on the GPU, got {pred.dtype} {tuple(pred.shape)} on {pred.device}')
+    pred = pred.detach().contiguous()
+    B, T, _, n, _ = (int(v) for v in pred.shape)
+    N = int(data.shape[-1])
+    if not torch.is_tensor(data) or tuple(data.shape) != (B, T, 6, N, N) or N % 2 or N not in (n, 2 * n):
+        raise ValueError(f'smoke score: data {tuple(data.shape)} against pred {tuple(pred.shape)}: [B, T, 6, N, N] with N = n or 2 n (even) is needed')
+    table = _channel_table([data[:, :, c] for c in range(6)], (B, T, N, N), pred.device)
+    with torch.cuda.device(pred.device):
+        out = torch.empty(B, 4, 5, dtype=torch.float64, device=pred.device)
+        _lib.check(_lib.load().wdno_smoke_score_super(_p(pred), table, _p(out), B, T, n, N, _stream()), 'wdno_smoke_score_super')
+    s = out.cpu().numpy().transpose(1, 0, 2)                                  # [4, B, 5]
+    cells = np.array([T * g * g for g in (N // 2, n, N, N)], dtype=np.float64).reshape(4, 1)
+    return _metrics(s, cells, w_energy)
 
 
 def control_channels(pred, density, velocity, ratio):
