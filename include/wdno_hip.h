@@ -952,6 +952,39 @@ typedef struct {
 int wdno_burgers_score(const float* u, const float* f, const float* x_gt, const float* u_target, double* out,
                        const wdno_burgers_score_desc* d, wdno_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------ Burgers evaluation: the super-resolution cascade
+ * wdno_burgers_cascade_conditions: the hand-off between two levels of evaluate()'s cascade (eval_ddpm_burgers.py:306-338; test_util.py:185-196)
+ * in one launch that writes EVERY element of the super level's condition source src [B][17][P_t][P_x] (fp32, contiguous, 16-byte aligned,
+ * network units), in place of upsample_coef, the pad, the division, get_target(is_wave=True), its slices and divisions, and the zeroed tensor
+ * and three copies of GaussianDiffusion._sampling_setup:
+ *   src[b, 8 + c, i, j] = x_prev[b, c, i / 2, j / 2] / rescaler[8 + c]        i < 2 h0, j < 2 w0, c < 8; 0 beyond. One IEEE division: with
+ *                                                                            x_prev = sample * rescaler the reference's (x r) / r bit for bit
+ *   src[b, 16, i, j]    = band(i / (P_t / 4))[j] / rescaler[16]              j < n_x / 2; 0 beyond, and 0 where the stripe's flag is off
+ *   src[b, 0..7]        = 0
+ * x_prev: the previous level's returned block [B][8][h0][w0] with element strides (columns contiguous). 2 h0 = h1 + 1 is one row more than
+ * the fine block (h1, w1): the ps[0] + 1 rows the sampler copies. band(0), band(1) are the low and high band of the one-level periodized
+ * analysis (L = 10) of u_target[b, 0, :n_x], band(2), band(3) those of u_target[b, n_t - 1, :n_x] (flags cond_u0 / cond_uT), with
+ * band[k] = sum_m dec[L - 1 - m] u[(2 k + m - (L / 2 - 1)) mod n_x], accumulated in fp32 in the order m = 0 .. L - 1. u_target is read in
+ * place: element (b, r, c) at u_target[b tgt_sample_stride + r tgt_row_stride + c tgt_col_stride], strides in elements. rescaler [17]; filt
+ * as for wdno_burgers_guidance. A workgroup per (tile of `tile` rows, channel, sample); lds_bytes = 16 P_x. Requires 2 h0 == h1 + 1,
+ * 2 w0 == w1 == n_x / 2, 2 h0 <= P_t, 2 w0 <= P_x, P_t % 4 == 0, P_x % 4 == 0, P_x <= 2048, n_x >= L, ntile == ceil(P_t / tile), C == 17:
+ * WDNO_EINVAL otherwise; WDNO_EUNSUPPORTED for anything but mode 0 (periodization) with L = 10 (bior2.4). Nothing is written then, and nothing
+ * is allocated. No atomics, a fixed order: a sample's bits do not depend on B or its index. */
+typedef struct {
+  long long prev_sample_stride;                                 /* x_prev, in elements; columns are contiguous */
+  long long tgt_sample_stride, tgt_row_stride, tgt_col_stride;  /* u_target */
+  int prev_chan_stride, prev_row_stride;
+  int B, C, h0, w0, h1, w1;                                     /* previous block, fine block */
+  int n_t, n_x;                                                 /* the level's target: rows 0 and n_t - 1, columns 0 .. n_x - 1 are read */
+  int P_t, P_x;
+  int tile, ntile;
+  int cond_u0, cond_uT;
+  int L, mode;
+  int lds_bytes, reserved;
+} wdno_burgers_cascade_desc;
+int wdno_burgers_cascade_conditions(const float* x_prev, const float* u_target, const float* rescaler, float* src,
+                                    const wdno_burgers_cascade_desc* d, const float* filt, wdno_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,12 @@ class BurgersReconstructDesc(C.Structure):  # include/wdno_hip.h: wdno_burgers_r
                [(k, I) for k in ('chan_stride', 'row_stride', 'h', 'w', 'n_t', 'n_x', 'L', 'mode', 'tn', 'ntile', 'lds_bytes', 'reserved')]
 
 
+class BurgersCascadeDesc(C.Structure):      # include/wdno_hip.h: wdno_burgers_cascade_desc
+    _fields_ = [(k, C.c_longlong) for k in ('prev_sample_stride', 'tgt_sample_stride', 'tgt_row_stride', 'tgt_col_stride')] + \
+               [(k, I) for k in ('prev_chan_stride', 'prev_row_stride', 'B', 'C', 'h0', 'w0', 'h1', 'w1', 'n_t', 'n_x', 'P_t', 'P_x', 'tile', 'ntile',
+                                 'cond_u0', 'cond_uT', 'L', 'mode', 'lds_bytes', 'reserved')]
+
+
 class BurgersScoreDesc(C.Structure):        # include/wdno_hip.h: wdno_burgers_score_desc
     _fields_ = [(k, I) for k in ('B', 'n_t', 'n_x', 'sub')] + \
                [(k, C.c_longlong) for k in ('gt_sample_stride', 'gt_row_stride', 'gt_col_stride', 'ut_sample_stride', 'ut_row_stride', 'ut_col_stride')] + \
@@ -283,6 +289,7 @@ PROTOTYPES = {
     'wdno_smoke_score_super': (I, [P, C.POINTER(SmokeScoreChannel), P, I, I, I, I, P]),
     'wdno_burgers_reconstruct': (I, [P, P, P, P, C.POINTER(BurgersReconstructDesc), PF, P]),
     'wdno_burgers_score': (I, [P, P, P, P, P, C.POINTER(BurgersScoreDesc), P]),
+    'wdno_burgers_cascade_conditions': (I, [P, P, P, P, C.POINTER(BurgersCascadeDesc), PF, P]),
 }
 
 _lib = None

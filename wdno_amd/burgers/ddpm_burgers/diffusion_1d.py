@@ -234,6 +234,19 @@ class GaussianDiffusion(nn.Module):
         pred = mean if noise is None else mean + (0.5 * logvar).exp() * noise
         return pred, x_start, pred_noise
 
+    _cond_src = None
+
+    def sample_with_source(self, cond_src, **kwargs):
+        """sample(**kwargs) with the condition source handed over assembled (an extension; sample, p_sample_loop and ddim_sample keep the
+        reference's parameter lists): cond_src is a contiguous fp32 tensor of the sampled shape on the sampling device whose conditioned
+        positions hold the clean values (burgers/cascade.py: super_conditions). It is used as it is instead of a zeroed tensor and the
+        copies; low, u_init and u_final are still passed, as views of it, for the shapes."""
+        self._cond_src = cond_src
+        try:
+            return self.sample(**kwargs)
+        finally:
+            self._cond_src = None
+
     def _sampling_setup(self, shape, kwargs):
         device = self.betas.device
         if not self.is_super_model:
@@ -242,6 +255,15 @@ class GaussianDiffusion(nn.Module):
             ps = self.padded_shape[kwargs['N_upsample'] - 1]
             coef_shape = [ps[0] + 1, ps[1]]
         cw = int(coef_shape[-1])
+        cond_src = self._cond_src
+        if cond_src is not None:                # handed over assembled (sample_with_source): the conditions give the shapes only
+            if tuple(cond_src.shape) != tuple(shape) or cond_src.dtype != torch.float32 or cond_src.device != torch.device(device) or \
+                    not cond_src.is_contiguous():
+                raise ValueError(f'cond_src must be a contiguous float32 {tuple(shape)} tensor on {device}, got {cond_src.dtype} '
+                                 f'{tuple(cond_src.shape)} on {cond_src.device}')
+            u_rows = kwargs['u_init'].shape[-2] if self.is_condition_u0 else 0
+            uT_rows = kwargs['u_final'].shape[-2] if self.is_condition_uT else 0
+            return cond_src, self._desc(shape, coef_shape, u_rows, uT_rows)
         src = torch.zeros(tuple(shape), device=device, dtype=torch.float32)
         u_rows = uT_rows = 0
         if self.is_condition_u0:

@@ -17,9 +17,19 @@ end to end in one process:
                       keyed on the object's identity -- is replayed on every batch instead of being captured again
   save_eval_results   the reference's 15 YAML entries per resolution through result_io.save_acc
 
-Out of scope, raising NotImplementedError with the reference's line: is_wavelet=False (eval_ddpm_burgers.py:126-132, 180-182, 196-197),
-is_super_model=True and the cascade loop (:254-258, 306-338), the three-way MSE of the super model (:207-218). Anything else falls through
-to the reference's module when that is on sys.path behind this tree."""
+and, with `--is_super_model True --upsample_t k --upsample_x k --super_exp_id ...` (two checkpoints), the zero-shot super-resolution cascade
+of l.254-258, 306-338 after every base batch:
+
+  evaluate            per level k = 1 .. upsample_x one launch (wdno_amd.burgers.cascade.super_conditions, csrc/burgers_cascade.hip) writes
+                      the super model's whole condition source from the previous level's block and two rows of the level's target, read
+                      in place from the held test file (wdno_amd.burgers.cascade.get_target_view); the level samples unguided (the reference's wu = wf = 0)
+  diffuse_2dconv      N_upsample=k takes entry k - 1 of the model's shape lists; cond_src= (an extension) goes to sample_with_source; the
+                      reconstruction reads channels 0-7 of the 17-channel sample; the solver runs 80 2^k records on the level's forcing
+
+Out of scope, raising NotImplementedError with the reference's line: is_wavelet=False (eval_ddpm_burgers.py:126-132, 180-182, 196-197);
+is_super_model=True with upsample_x=0 (:307, a cascade without a level to run); N_upsample / low without args.is_super_model (:175-178);
+is_super_model together with is_condition_f, the three-way interpolation MSE (:207-218). Anything else falls through to the reference's
+module when that is on sys.path behind this tree."""
 import argparse
 import math
 
@@ -30,7 +40,8 @@ import wdno_amd
 from ddpm_burgers.generate_burgers import burgers_numeric_solve_free          # looked up as a module global at call time
 from ddpm_burgers.model_utils import get_scheduler
 from ddpm_burgers.test_util import (SOLVER_N_UPSAMPLE, ddpm_guidance_loss, get_target, load_2dconv_base_model,  # noqa: F401
-                                    load_2dconv_super_model, metric, mse_deviation)
+                                    metric, mse_deviation)
+from wdno_amd.burgers.cascade import get_target_view, load_super_model as load_2dconv_super_model      # ddpm_burgers.test_util's still refuses
 from result_io import save_acc          # this tree's top-level module (see its docstring)
 
 _reference_getattr = wdno_amd.reference_fallthrough('eval_ddpm_burgers', __file__)
@@ -114,14 +125,22 @@ def diffuse_2dconv(ddpm, args, custom_metric, ret_ls=False, RESCALER=1, **kwargs
     where the reference has float32; any other custom_metric gives what it returns, converted as the reference converts it."""
     from wdno_amd.burgers.reconstruct import reconstruct
     from wdno_amd.burgers import score as S
-    if 'N_upsample' in kwargs or 'low' in kwargs or getattr(args, 'is_super_model', False):
-        _unsupported('is_super_model=True (N_upsample, low)', '175-178, 189-190, 207-218')
+    is_super = bool(getattr(args, 'is_super_model', False))
+    if ('N_upsample' in kwargs or 'low' in kwargs) and not is_super:
+        _unsupported('N_upsample / low without args.is_super_model', '175-178, 189-190')
+    if is_super and getattr(args, 'is_condition_f', False):
+        _unsupported('is_super_model=True with is_condition_f=True (the three-way interpolation MSE)', '207-218')
     if not ddpm.is_wavelet or not getattr(args, 'is_wavelet', True):
         _unsupported('is_wavelet=False', '180-182, 196-197')
-    shape, ori_shape, N_upsample = ddpm.padded_shape, ddpm.ori_shape, 0
+    cond_src = kwargs.pop('cond_src', None)          # an extension: the super level's condition source, assembled (burgers/cascade.py)
+    if 'N_upsample' not in kwargs:
+        shape, ori_shape, N_upsample = ddpm.padded_shape, ddpm.ori_shape, 0
+    else:
+        N_upsample = int(kwargs['N_upsample'])
+        shape, ori_shape = ddpm.padded_shape[N_upsample - 1], ddpm.ori_shape[N_upsample - 1]
     h, w, n_x = int(shape[-2]), int(shape[-1]), int(ori_shape[-1])
 
-    sample = ddpm.sample(**kwargs)
+    sample = ddpm.sample(**kwargs) if cond_src is None else ddpm.sample_with_source(cond_src, **kwargs)
     u, f = reconstruct(sample, shape, ori_shape, RESCALER, args.wave_type, args.pad_mode)
     r = torch.as_tensor(RESCALER, dtype=torch.float32).reshape(-1).to(sample.device)
     x = sample[:, :8, :h, :w] * (r if r.numel() == 1 else r[:8].reshape(1, 8, 1, 1))
@@ -154,16 +173,32 @@ def diffuse_2dconv(ddpm, args, custom_metric, ret_ls=False, RESCALER=1, **kwargs
 
 # ------------------------------------------------------------------------------------------------ the whole test set
 def evaluate(model_i, super_model_i, args, Ntest=50, batch_size=25, wu=0, wf=0, RESCALER=1):
-    """The evaluation of eval_ddpm_burgers.py:244-344 for the base model: [[ddpm_mse, the J_diffused rows, the J_actual rows, energy,
-    total_J]], every entry an array over the Ntest samples."""
-    if args.is_super_model:
-        _unsupported('is_super_model=True and the cascade loop', '254-258, 306-338')
+    """The evaluation of eval_ddpm_burgers.py:244-344: per resolution k = 0 .. upsample_x (0 alone without is_super_model) the list
+    [ddpm_mse, the J_diffused rows, the J_actual rows, energy, total_J], every entry an array over the Ntest samples.
+
+    With is_super_model the zero-shot cascade of l.306-338 follows every base batch: per level one launch (burgers/cascade.py:
+    super_conditions) turns the previous level's returned block and two rows of the level's target -- a strided view of the held test file
+    -- into the super model's condition source, which diffuse_2dconv hands to sample_with_source. The super levels sample unguided, through
+    the graph-replayed loop: the reference passes wu = wf = 0 there (l.331), so its guidance adds an identically zero gradient; nor is f
+    transformed at those levels (the sampler reads it only under is_condition_f, which is out of scope with a super model)."""
     if not args.is_wavelet:
         _unsupported('is_wavelet=False', '126-132, 180-182, 196-197')
+    if args.is_super_model:                     # refusals before anything is loaded
+        if args.upsample_x < 1:
+            _unsupported('is_super_model=True with upsample_x=0 (a cascade without a super level)', '307')
+        if args.is_condition_f:
+            _unsupported('is_super_model=True with is_condition_f=True (the three-way interpolation MSE)', '207-218')
     ddpm = load_2dconv_base_model(model_i, args, RESCALER)
-    RESCALER_base = torch.as_tensor(RESCALER).cuda()
+    levels = 0
+    if args.is_super_model:
+        from wdno_amd.burgers import cascade as CS
+        ddpm_super = load_2dconv_super_model(super_model_i, args, RESCALER)
+        levels = args.upsample_x
+    RESCALER = torch.as_tensor(RESCALER).cuda()
+    RESCALER_base = RESCALER[:, 8:17] if args.is_super_model else RESCALER
+    rescaler_f32 = RESCALER.to(torch.float32).reshape(-1).contiguous()          # the table is int64: cast once, not in every hand-off
     rep = math.ceil(Ntest / batch_size)
-    logs = {0: {'mses': [], 'l_gts': [], 'l_dfs': [], 'energies': [], 'l_total': []}}
+    logs = {k: {'mses': [], 'l_gts': [], 'l_dfs': [], 'energies': [], 'l_total': []} for k in range(levels + 1)}
     sampled_coefs = []
     guidance = {}                          # batch size -> the BurgersGuidance whose captured step serves every batch of that size
 
@@ -203,6 +238,25 @@ def evaluate(model_i, super_model_i, args, Ntest=50, batch_size=25, wu=0, wf=0, 
         logs[0]['energies'].append(energy)
         logs[0]['l_total'].append(total_J)
         sampled_coefs.append(sampled_coef.cpu().numpy())
+
+        for k in range(1, levels + 1):          # zero-shot super-resolution (l.306-338)
+            pad_size = 64 * 2 ** k
+            src = CS.super_conditions(sampled_coef, get_target_view(args, target_idx, N_upsample=k, dataset=args.dataset), rescaler_f32,
+                                      ddpm_super.padded_shape[k - 1], pad_size, pad_size, args.is_condition_u0, args.is_condition_uT,
+                                      args.wave_type, args.pad_mode)
+            low, u_init, u_final = CS.views(src)
+            sampled_coef, ddpm_mse, J_diffused, J_actual, energy, total_J = diffuse_2dconv(
+                ddpm_super, args, N_upsample=k, RESCALER=RESCALER, batch_size=batch_size,
+                J_scheduler=get_scheduler(args.J_scheduler),
+                custom_metric=BurgersMetric(u_target_ori, args.upsample_t, wf, args.report_all),
+                cond_src=src, low=low, u_init=u_init, u_final=u_final,
+                x_gt=u_target_ori,
+            )
+            logs[k]['mses'].append(ddpm_mse)
+            logs[k]['l_gts'].append(J_actual)
+            logs[k]['l_dfs'].append(J_diffused)
+            logs[k]['energies'].append(energy)
+            logs[k]['l_total'].append(total_J)
 
     return [[np.concatenate(logs[k]['mses']),
              *(np.concatenate(logs[k]['l_dfs'], axis=1)[i] for i in range(logs[k]['l_dfs'][0].shape[0])),
