@@ -80,6 +80,25 @@ int wdno_dwt_inv_adjoint(const float* dx, float* dcoef, const wdno_dwt_desc* d, 
  * the 8 channels of an image is written: wdno_pack_smoke_fields(coef = NULL, ...) fills the rest of the state. */
 int wdno_dwt_fwd_packed(const float* x, float* state, const wdno_dwt_desc* d, const float* filters_host, int img_inner, int64_t cs_outer, int row_w,
                         const float* rescaler, wdno_stream_t s);
+/* What the wavelet entry points above launch for a descriptor (nothing is launched; the launch path asks the same code, and the query
+ * honours wdno_set_debug modes 11 and 45 and WDNO_DWT_LDS_KB exactly as the launch does). entry: WDNO_DWT_ENTRY_*.
+ * family: WDNO_DWT_PER_AXIS (one analysis_kernel / synthesis_kernel launch per axis through the workspace of wdno_dwt_ws_bytes) or the ONE
+ * fused kernel: WDNO_DWT_ANALYSIS / WDNO_DWT_ANALYSIS_PACKED (dwt_analysis_fused_kernel), WDNO_DWT_SYNTHESIS2 (dwt_synthesis2_kernel, 2-D, staged
+ * rows), WDNO_DWT_SYNTHESIS_FUSED (dwt_synthesis_fused_kernel), WDNO_DWT_SYNTHESIS3_STREAM (dwt_synthesis3_stream_kernel); -1 when rc != WDNO_OK.
+ * variant: PMAX (1, 2) of dwt_synthesis2_kernel, WMAX (4, 8) of the stream kernel, 0 otherwise. For a fused kernel nh = rows per tile
+ * (coefficient rows of an analysis, q rows of a synthesis), tiles_h, tiles_t, blocks = n_img * tiles_t * tiles_h and lds_bytes = the dynamic LDS
+ * of the launch; all 0 for the per-axis passes. rc = the code the entry point would return given the workspace of wdno_dwt_ws_bytes.
+ * WDNO_DWT_ENTRY_FWD_PACKED: the arguments of wdno_dwt_fwd_packed that are not in the descriptor are taken as img_inner = 1, cs_outer = 0, an
+ * aligned state and the narrowest legal row_w (out_dims[2] rounded up to 4). None of them enters the tile choice, so family, nh, tiles, blocks and
+ * lds_bytes are those of the launch; the descriptor's own strides are tested as the launch tests them (any of cs_img, cs_band, cs0, cs1 not a
+ * multiple of 4: WDNO_EUNSUPPORTED), but a launch can still refuse with WDNO_EUNSUPPORTED where the plan says WDNO_OK: for a misaligned state or
+ * cs_outer, a row_w that is below out_dims[2] or no multiple of 4, or a row_w so wide that an item index leaves the 32-bit division range.
+ * Returns WDNO_EINVAL only for out == NULL or an entry that is not listed. */
+enum { WDNO_DWT_ENTRY_FWD = 0, WDNO_DWT_ENTRY_INV = 1, WDNO_DWT_ENTRY_INV_ADJOINT = 2, WDNO_DWT_ENTRY_FWD_ADJOINT = 3, WDNO_DWT_ENTRY_FWD_PACKED = 4 };
+enum { WDNO_DWT_PER_AXIS = 0, WDNO_DWT_ANALYSIS = 1, WDNO_DWT_ANALYSIS_PACKED = 2, WDNO_DWT_SYNTHESIS2 = 3, WDNO_DWT_SYNTHESIS_FUSED = 4,
+       WDNO_DWT_SYNTHESIS3_STREAM = 5 };
+typedef struct { int family, variant, nh, tiles_h, tiles_t, blocks, lds_bytes, rc; } wdno_dwt_plan;
+int wdno_dwt_plan_query(const wdno_dwt_desc* d, int entry, wdno_dwt_plan* out);
 /* nearest x2 up-sampling of coefficient tensors (burgers/ddpm_burgers/wavelet_utils.py:5-16,
  * smoke/ddpm/wave_utils.py:1-14): in [outer, a, mid, b, c] -> out [outer, a*fa, mid, b*fb, c*fc]. */
 int wdno_upsample_coef(const float* in, float* out, int64_t outer, int a, int mid, int b, int c, int fa, int fb, int fc, wdno_stream_t s);

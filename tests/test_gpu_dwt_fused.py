@@ -50,16 +50,42 @@ CASES = [
     (3, 'periodization', 'bior2.4', (2, 16, 20, 24)),
     (3, 'periodization', 'bior2.2', (2, 7, 9, 12)),
     (3, 'periodization', 'db3', (1, 8, 10, 6)),
-    # the smallest shapes that reach the kernels no case above launches (by the arithmetic of fused_synthesis, csrc/dwt_synthesis.hip)
-    (2, 'periodization', 'bior2.4', (1, 12, 300)),          # dwt_synthesis2_kernel<.., PMAX = 2>: staged rows of 128 < RW = 156 <= 256 floats
-    (2, 'zero', 'bior1.3', (1, 10, 520)),                   # dwt_synthesis_fused_kernel<2, ..>: RW = 262 > 256
-    (3, 'periodization', 'bior2.4', (1, 10, 12, 80)),       # dwt_synthesis3_stream_kernel<.., WMAX = 8>: n_w = 1120 > 1024 W-pass items per frame
+    # the smallest shapes that reach the kernels no case above launches: REACHES below states which, and the plan query re-checks it
+    (2, 'periodization', 'bior2.4', (1, 12, 300)),
+    (2, 'zero', 'bior1.3', (1, 10, 520)),
+    (3, 'periodization', 'bior2.4', (1, 10, 12, 80)),
 ]
+# (family, variant) that ops.dwt_plan reports for the inverse of a case: PMAX = 2 of dwt_synthesis2_kernel (staged rows of 128 < RW <= 256 floats),
+# dwt_synthesis_fused_kernel<2, ..> (RW > 256), WMAX = 8 of dwt_synthesis3_stream_kernel (more than 1024 W-pass items per frame)
+REACHES = {
+    (2, 'periodization', 'bior2.4', (1, 12, 300)): ('synthesis2', 2),
+    (2, 'zero', 'bior1.3', (1, 10, 520)): ('synthesis_fused', 0),
+    (3, 'periodization', 'bior2.4', (1, 10, 12, 80)): ('synthesis3_stream', 8),
+}
+
+
+def inverse_plan(nd, mode, wave, shape):
+    """what idwt_packed launches for the coefficients of a signal of this shape"""
+    from wdno_amd import ops
+    from wdno_amd.filters import dwt_coeff_len
+    from wdno_amd.wavelets import MODES, _filters
+    L = _filters(wave)[1]
+    cd = [dwt_coeff_len(s, L, mode) for s in shape[-nd:]]
+    sig = [2 * c if MODES[mode] == 0 else 2 * c - L + 2 for c in cd]
+    c3 = [1] * (3 - nd) + cd
+    n_img = 1
+    for s in shape[:-nd]:
+        n_img *= s
+    cs = (2 ** nd * c3[0] * c3[1] * c3[2], c3[0] * c3[1] * c3[2], c3[1] * c3[2], c3[2])
+    return ops.dwt_plan('inv', nd, MODES[mode], L, n_img, [1] * (3 - nd) + sig, c3, cs)
 
 
 @pytest.mark.parametrize('nd,mode,wave,shape', CASES)
 def test_fused_equals_per_axis_bit_exact(W, nd, mode, wave, shape):
     wavelets, lib = W
+    if (nd, mode, wave, shape) in REACHES:
+        p = inverse_plan(nd, mode, wave, shape)
+        assert p['rc'] == 0 and (p['family'], p['variant']) == REACHES[(nd, mode, wave, shape)] and p['lds_bytes'] <= 65536, p
     g = torch.Generator().manual_seed(hash((nd, mode, wave, shape)) % 1000)
     x = torch.randn(*shape, generator=g).to(DEV)
     fa, fb = both(lib, lambda: wavelets.dwt_packed(x, wave, mode, nd))

@@ -62,6 +62,14 @@ class LayerNormPlan(C.Structure):            # include/wdno_hip.h: wdno_ln_plan
     _fields_ = [(k, I) for k in ('tpr', 'vpl', 'rows_per_block', 'blocks', 'max_rows_walk', 'rc')]
 
 
+class DwtPlan(C.Structure):                  # include/wdno_hip.h: wdno_dwt_plan
+    _fields_ = [(k, I) for k in ('family', 'variant', 'nh', 'tiles_h', 'tiles_t', 'blocks', 'lds_bytes', 'rc')]
+
+
+DWT_ENTRIES = ('fwd', 'inv', 'inv_adjoint', 'fwd_adjoint', 'fwd_packed')                                     # WDNO_DWT_ENTRY_*
+DWT_FAMILIES = ('per_axis', 'analysis', 'analysis_packed', 'synthesis2', 'synthesis_fused', 'synthesis3_stream')   # WDNO_DWT_*; -1: none
+
+
 class ConvWgradPlan(C.Structure):            # include/wdno_hip.h: wdno_wgrad_plan
     _fields_ = [(k, I) for k in ('family', 'bm', 'bn', 'splits', 'pix_per_split', 'splitpair', 'reduce_tiled', 'items', 'grid')]
 
@@ -146,6 +154,7 @@ PROTOTYPES = {
     'wdno_last_hip_error': (C.c_char_p, []),
     'wdno_set_debug': (I, [I]),
     'wdno_dwt_ws_bytes': (Z, [PD]),
+    'wdno_dwt_plan_query': (I, [PD, I, P]),
     'wdno_dwt_fwd': (I, [P, P, PD, PF, P, Z, P]),
     'wdno_dwt_fwd_packed': (I, [P, P, PD, PF, I, L, I, P, P]),
     'wdno_dwt_inv': (I, [P, P, PD, PF, P, Z, P]),

@@ -141,9 +141,10 @@ size_t dwt_fused_lds_budget(long default_kb) {
 }
 
 // true = the transform was launched as ONE fused kernel; false = not covered (1-D, long filters, rows that do not fit LDS, the
-// odd-length synthesis-shaped adjoint), the caller falls back to the per-axis passes.
+// odd-length synthesis-shaped adjoint), the caller falls back to the per-axis passes. With `plan` (wdno_dwt_plan_query) the same decision is
+// only reported: the units' "decide" step runs, their "launch" step does not.
 static bool fused_try(bool analysis_dir, const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st,
-                      const PackedStore* pk = nullptr) {
+                      const PackedStore* pk = nullptr, wdno_dwt_plan* plan = nullptr) {
   if ((wdno_debug_mode == WDNO_DBG_PER_AXIS_DWT_AND_WGRAD_WINDOW_K64 && !pk) || d->nd < 2) return false;
   if (!analysis_dir && d->mode == 0 && odd_rule)
     for (int a = 3 - d->nd; a < 3; ++a)
@@ -151,7 +152,7 @@ static bool fused_try(bool analysis_dir, const float* src, float* dst, const wdn
   if (!analysis_dir && d->mode == 0)
     for (int a = 3 - d->nd; a < 3; ++a)
       if (d->in_dims[a] != 2 * d->out_dims[a]) return false;
-  return analysis_dir ? dwt_fused_analysis(src, dst, d, taps, odd_rule, st, pk) : dwt_fused_synthesis(src, dst, d, taps, st);
+  return analysis_dir ? dwt_fused_analysis(src, dst, d, taps, odd_rule, st, pk, plan) : dwt_fused_synthesis(src, dst, d, taps, st, plan);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -169,11 +170,33 @@ static int validate(const wdno_dwt_desc* d) {
   return WDNO_OK;
 }
 
-struct Plan {
-  int nax;
-  int ax[3];           // axis ids (0=T,1=H,2=W in the 3-slot convention), in forward (analysis) order
-  int64_t sig_elems[4];   // number of elements of the intermediate tensor before pass i (i=0: the signal)
+// What each entry point (WDNO_DWT_ENTRY_*) runs with -- the filter pair (decomposition or reconstruction), its tap order, the direction of the
+// data and whether an odd periodized length follows the repeated-sample rule -- and what it asks of the descriptor beyond validate(): ONE
+// table and ONE check, for the entry points and for wdno_dwt_plan_query.
+//   inv_adjoint: d(coef) from d(x) for x = inv(coef): analysis-shaped with reversed reconstruction taps
+//   fwd_adjoint: d(x) from d(coef) for coef = fwd(x): synthesis-shaped with reversed decomposition taps
+struct EntrySpec { bool rec_taps, reverse_taps, analysis_dir, odd_rule; };
+static const EntrySpec ENTRIES[5] = {
+  {false, false, true, true},      // WDNO_DWT_ENTRY_FWD
+  {true, false, false, false},     // WDNO_DWT_ENTRY_INV
+  {true, true, true, false},       // WDNO_DWT_ENTRY_INV_ADJOINT
+  {false, true, false, true},      // WDNO_DWT_ENTRY_FWD_ADJOINT
+  {false, false, true, true},      // WDNO_DWT_ENTRY_FWD_PACKED
 };
+static int entry_check(const wdno_dwt_desc* d, int entry) {
+  int rc = validate(d);
+  if (rc) return rc;
+  if (entry == WDNO_DWT_ENTRY_FWD_PACKED && (d->nd != 3 || d->mode != 1)) return WDNO_EUNSUPPORTED;
+  for (int a = 3 - d->nd; a < 3; ++a) {
+    if (entry == WDNO_DWT_ENTRY_INV || entry == WDNO_DWT_ENTRY_INV_ADJOINT) {
+      int want = d->mode == 1 ? 2 * d->out_dims[a] - d->L + 2 : 2 * d->out_dims[a];
+      if (d->in_dims[a] != want) return WDNO_EINVAL;   // the inverse always produces the natural (even) length
+    } else if (d->mode == 1 && d->out_dims[a] != (d->in_dims[a] + d->L - 1) / 2) {
+      return WDNO_EINVAL;
+    }
+  }
+  return WDNO_OK;
+}
 
 // Intermediate layouts (forward order T, H, W; nb = number of bands produced so far):
 //   after pass T : [img][bt][To][H][W]
@@ -215,10 +238,14 @@ static void set_outer(OuterMap& om, int ncomp, const int* n, const int64_t* sa, 
 // Build the pass descriptors shared by all four entry points. `analysis_dir`: true when data flows
 // signal -> coefficients (dwt_fwd, dwt_inv_adjoint), false for the reverse direction.
 // sig = the signal-side tensor of the whole transform, coef = the packed coefficient tensor.
-static int run(const float* src, float* dst, const wdno_dwt_desc* d, const float* fl, const float* fh, bool reverse_taps,
-               bool analysis_dir, bool odd_rule, void* ws, size_t ws_bytes, hipStream_t st) {
+static int run(const float* src, float* dst, const wdno_dwt_desc* d, int entry, const float* f, void* ws, size_t ws_bytes, hipStream_t st) {
+  int rc = entry_check(d, entry);
+  if (rc) return rc;
+  const EntrySpec& e = ENTRIES[entry];
+  const bool analysis_dir = e.analysis_dir, odd_rule = e.odd_rule;
+  const float* fl = f + (e.rec_taps ? 2 * d->L : 0);
   Taps taps;
-  fill_taps(taps, fl, fh, d->L, reverse_taps);
+  fill_taps(taps, fl, fl + d->L, d->L, e.reverse_taps);
   if (fused_try(analysis_dir, src, dst, d, taps, odd_rule, st)) return wdno_check_launch();
   if (ws_elems(d) * sizeof(float) > ws_bytes) return WDNO_EWORKSPACE;
   const int T = d->in_dims[0], H = d->in_dims[1], W = d->in_dims[2];
@@ -299,11 +326,7 @@ static int run(const float* src, float* dst, const wdno_dwt_desc* d, const float
 }
 
 extern "C" int wdno_dwt_fwd(const float* x, float* coef, const wdno_dwt_desc* d, const float* f, void* ws, size_t ws_bytes, wdno_stream_t s) {
-  int rc = validate(d);
-  if (rc) return rc;
-  for (int a = 3 - d->nd; a < 3; ++a)
-    if (d->mode == 1 && d->out_dims[a] != (d->in_dims[a] + d->L - 1) / 2) return WDNO_EINVAL;
-  return run(x, coef, d, f, f + d->L, false, true, true, ws, ws_bytes, as_stream(s));
+  return run(x, coef, d, WDNO_DWT_ENTRY_FWD, f, ws, ws_bytes, as_stream(s));
 }
 // Analysis with the coefficients stored straight into a larger, differently ordered tensor and divided by a per-channel constant: image
 // i = (outer, inner) = (i / img_inner, i % img_inner) writes at outer * cs_outer + inner * d->cs_img (+ band * cs_band + k0 * cs0 + k1 * cs1 + k2),
@@ -314,42 +337,38 @@ extern "C" int wdno_dwt_fwd(const float* x, float* coef, const wdno_dwt_desc* d,
 // kernel does not take is WDNO_EUNSUPPORTED (the caller then transforms into a coefficient tensor and packs, wdno_pack_smoke_fields).
 extern "C" int wdno_dwt_fwd_packed(const float* x, float* state, const wdno_dwt_desc* d, const float* f, int img_inner, int64_t cs_outer, int row_w,
                                    const float* rescaler, wdno_stream_t s) {
-  int rc = validate(d);
-  if (rc) return rc;
+  if (!d) return WDNO_EINVAL;
   WDNO_REQUIRE(x && state && f && rescaler && img_inner > 0 && d->n_img % img_inner == 0);
-  if (d->nd != 3 || d->mode != 1) return WDNO_EUNSUPPORTED;
-  for (int a = 0; a < 3; ++a)
-    if (d->out_dims[a] != (d->in_dims[a] + d->L - 1) / 2) return WDNO_EINVAL;
+  int rc = entry_check(d, WDNO_DWT_ENTRY_FWD_PACKED);            // validate() and what this entry asks beyond it
+  if (rc) return rc;
+  const EntrySpec& e = ENTRIES[WDNO_DWT_ENTRY_FWD_PACKED];
   Taps taps;
-  fill_taps(taps, f, f + d->L, d->L, false);
+  fill_taps(taps, f, f + d->L, d->L, e.reverse_taps);
   PackedStore ps = {img_inner, row_w, cs_outer, rescaler};
-  if (!fused_try(true, x, state, d, taps, true, as_stream(s), &ps)) return WDNO_EUNSUPPORTED;
+  if (!fused_try(e.analysis_dir, x, state, d, taps, e.odd_rule, as_stream(s), &ps)) return WDNO_EUNSUPPORTED;
   return wdno_check_launch();
 }
 extern "C" int wdno_dwt_inv(const float* coef, float* x, const wdno_dwt_desc* d, const float* f, void* ws, size_t ws_bytes, wdno_stream_t s) {
-  int rc = validate(d);
-  if (rc) return rc;
-  for (int a = 3 - d->nd; a < 3; ++a) {
-    int want = d->mode == 1 ? 2 * d->out_dims[a] - d->L + 2 : 2 * d->out_dims[a];
-    if (d->in_dims[a] != want) return WDNO_EINVAL;   // the inverse always produces the natural (even) length
-  }
-  return run(coef, x, d, f + 2 * d->L, f + 3 * d->L, false, false, false, ws, ws_bytes, as_stream(s));
+  return run(coef, x, d, WDNO_DWT_ENTRY_INV, f, ws, ws_bytes, as_stream(s));
 }
-// d(coef) from d(x) for x = inv(coef): analysis-shaped with reversed reconstruction taps
 extern "C" int wdno_dwt_inv_adjoint(const float* dx, float* dcoef, const wdno_dwt_desc* d, const float* f, void* ws, size_t ws_bytes, wdno_stream_t s) {
-  int rc = validate(d);
-  if (rc) return rc;
-  for (int a = 3 - d->nd; a < 3; ++a) {
-    int want = d->mode == 1 ? 2 * d->out_dims[a] - d->L + 2 : 2 * d->out_dims[a];
-    if (d->in_dims[a] != want) return WDNO_EINVAL;
-  }
-  return run(dx, dcoef, d, f + 2 * d->L, f + 3 * d->L, true, true, false, ws, ws_bytes, as_stream(s));
+  return run(dx, dcoef, d, WDNO_DWT_ENTRY_INV_ADJOINT, f, ws, ws_bytes, as_stream(s));
 }
-// d(x) from d(coef) for coef = fwd(x): synthesis-shaped with reversed decomposition taps
 extern "C" int wdno_dwt_fwd_adjoint(const float* dcoef, float* dx, const wdno_dwt_desc* d, const float* f, void* ws, size_t ws_bytes, wdno_stream_t s) {
-  int rc = validate(d);
-  if (rc) return rc;
-  for (int a = 3 - d->nd; a < 3; ++a)
-    if (d->mode == 1 && d->out_dims[a] != (d->in_dims[a] + d->L - 1) / 2) return WDNO_EINVAL;
-  return run(dcoef, dx, d, f, f + d->L, true, false, true, ws, ws_bytes, as_stream(s));
+  return run(dcoef, dx, d, WDNO_DWT_ENTRY_FWD_ADJOINT, f, ws, ws_bytes, as_stream(s));
+}
+// What the entry point would launch (include/wdno_hip.h): entry_check and fused_try as the entry points call them, with `plan` set
+extern "C" int wdno_dwt_plan_query(const wdno_dwt_desc* d, int entry, wdno_dwt_plan* out) {
+  if (!out || entry < WDNO_DWT_ENTRY_FWD || entry > WDNO_DWT_ENTRY_FWD_PACKED) return WDNO_EINVAL;
+  *out = wdno_dwt_plan{-1, 0, 0, 0, 0, 0, 0, WDNO_OK};
+  if ((out->rc = entry_check(d, entry))) return WDNO_OK;
+  const EntrySpec& e = ENTRIES[entry];
+  Taps taps = {};
+  const bool packed = entry == WDNO_DWT_ENTRY_FWD_PACKED;
+  PackedStore ps = {1, (d->out_dims[2] + 3) & ~3, 0, nullptr};
+  wdno_dwt_plan pl;
+  if (fused_try(e.analysis_dir, nullptr, nullptr, d, taps, e.odd_rule, nullptr, packed ? &ps : nullptr, &pl)) *out = pl;
+  else if (packed) out->rc = WDNO_EUNSUPPORTED;
+  else out->family = WDNO_DWT_PER_AXIS;
+  return WDNO_OK;
 }

@@ -170,9 +170,10 @@ __global__ __launch_bounds__(256) void dwt_analysis_fused_kernel(const float* __
   }
 }
 
+// decide: the tile geometry and the kernel of an analysis, nothing launched. false = not covered by the fused kernel.
 template <int ND, int L, int MODE>
-static bool fused_analysis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk) {
-  FusedGeom g = dw_geom(d, L, MODE);
+static bool analysis_decide(const float* dst, const wdno_dwt_desc* d, bool odd_rule, const PackedStore* pk, FusedGeom& g, FusedChoice& c) {
+  g = dw_geom(d, L, MODE);
   const bool odd = MODE == 0 && odd_rule;
   g.odd_t = odd && (g.T & 1); g.odd_h = odd && (g.H & 1); g.odd_w = odd && (g.W & 1);
   g.FW = (ND == 2 && MODE == 0) ? 2 * g.Wo : 2 * g.Wo + L - 2;        // 2-D periodization: one period per LDS row (see the kernel)
@@ -204,38 +205,60 @@ static bool fused_analysis(const float* src, float* dst, const wdno_dwt_desc* d,
   g.n_blocks = (int)nb;
   g.dFW = make_fastdiv(g.FW); g.dNH = make_fastdiv(g.NH); g.dWo = make_fastdiv(g.Wo); g.dQW4 = make_fastdiv((g.Wo + 3) / 4);
   if ((int64_t)2 * NK * 2 * g.NH * std::max(g.FW, g.Wo) * (int64_t)std::max(g.FW, g.NH) >= (1ll << 32)) return false;   // fd_div range
+  c = FusedChoice{WDNO_DWT_ANALYSIS, 0, lds};
   if (pk) {
-    if constexpr (ND == 3 && MODE == 1) {        // the smoke pipeline's transform (zero mode, 3-D); other shapes: not instantiated
-      g.img_inner = pk->img_inner; g.cs_outer = pk->cs_outer; g.resc = pk->resc; g.row_w = pk->row_w;
-      g.dInner = make_fastdiv(g.img_inner);
-      g.dQW4 = make_fastdiv(g.row_w / 4);
-      if (g.row_w < g.Wo || (g.row_w & 3) || ((g.cs_img | g.cs_band | g.cs0 | g.cs1 | g.cs_outer) & 3) || ((uintptr_t)dst & 15)) return false;
-      if ((int64_t)2 * NK * 2 * g.NH * g.row_w * (int64_t)std::max(g.FW, g.NH) >= (1ll << 32)) return false;   // fd_div range
-      if ((int64_t)g.n_img * g.img_inner >= (1ll << 32)) return false;
-      dwt_analysis_fused_kernel<ND, L, MODE, NK, true><<<(int)nb, 256, lds, st>>>(src, dst, g, taps);
-      return true;
-    }
-    return false;
+    if (!(ND == 3 && MODE == 1)) return false;   // the smoke pipeline's transform (zero mode, 3-D); other shapes: not instantiated
+    g.img_inner = pk->img_inner; g.cs_outer = pk->cs_outer; g.resc = pk->resc; g.row_w = pk->row_w;
+    g.dInner = make_fastdiv(g.img_inner);
+    g.dQW4 = make_fastdiv(g.row_w / 4);
+    if (g.row_w < g.Wo || (g.row_w & 3) || ((g.cs_img | g.cs_band | g.cs0 | g.cs1 | g.cs_outer) & 3) || ((uintptr_t)dst & 15)) return false;
+    if ((int64_t)2 * NK * 2 * g.NH * g.row_w * (int64_t)std::max(g.FW, g.NH) >= (1ll << 32)) return false;   // fd_div range
+    if ((int64_t)g.n_img * g.img_inner >= (1ll << 32)) return false;
+    c.family = WDNO_DWT_ANALYSIS_PACKED;
   }
-  dwt_analysis_fused_kernel<ND, L, MODE, NK><<<(int)nb, 256, lds, st>>>(src, dst, g, taps);
+  return true;
+}
+
+// launch: what analysis_decide chose
+template <int ND, int L, int MODE>
+static void analysis_launch(const FusedChoice& c, const float* src, float* dst, const FusedGeom& g, const Taps& taps, hipStream_t st) {
+  constexpr int NK = (ND == 3) ? 3 : 4;
+  if (c.family == WDNO_DWT_ANALYSIS_PACKED) {
+    if constexpr (ND == 3 && MODE == 1) dwt_analysis_fused_kernel<ND, L, MODE, NK, true><<<g.n_blocks, 256, c.lds, st>>>(src, dst, g, taps);
+    return;
+  }
+  dwt_analysis_fused_kernel<ND, L, MODE, NK><<<g.n_blocks, 256, c.lds, st>>>(src, dst, g, taps);
+}
+
+template <int ND, int L, int MODE>
+static bool fused_analysis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk,
+                           wdno_dwt_plan* plan) {
+  FusedGeom g;
+  FusedChoice c;
+  if (!analysis_decide<ND, L, MODE>(dst, d, odd_rule, pk, g, c)) return false;
+  if (plan) dw_plan_of(g, c, plan);
+  else analysis_launch<ND, L, MODE>(c, src, dst, g, taps, st);
   return true;
 }
 
 template <int ND, int L>
-static bool fused_analysis_mode(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk) {
-  return d->mode == 1 ? fused_analysis<ND, L, 1>(src, dst, d, taps, odd_rule, st, pk) : fused_analysis<ND, L, 0>(src, dst, d, taps, odd_rule, st, pk);
+static bool fused_analysis_mode(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk,
+                                wdno_dwt_plan* plan) {
+  return d->mode == 1 ? fused_analysis<ND, L, 1>(src, dst, d, taps, odd_rule, st, pk, plan) : fused_analysis<ND, L, 0>(src, dst, d, taps, odd_rule, st, pk, plan);
 }
 template <int ND>
-static bool fused_analysis_nd(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk) {
+static bool fused_analysis_nd(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk,
+                              wdno_dwt_plan* plan) {
   switch (d->L) {
-    case 2: return fused_analysis_mode<ND, 2>(src, dst, d, taps, odd_rule, st, pk);
-    case 4: return fused_analysis_mode<ND, 4>(src, dst, d, taps, odd_rule, st, pk);
-    case 6: return fused_analysis_mode<ND, 6>(src, dst, d, taps, odd_rule, st, pk);
-    case 8: return fused_analysis_mode<ND, 8>(src, dst, d, taps, odd_rule, st, pk);
-    case 10: return fused_analysis_mode<ND, 10>(src, dst, d, taps, odd_rule, st, pk);
+    case 2: return fused_analysis_mode<ND, 2>(src, dst, d, taps, odd_rule, st, pk, plan);
+    case 4: return fused_analysis_mode<ND, 4>(src, dst, d, taps, odd_rule, st, pk, plan);
+    case 6: return fused_analysis_mode<ND, 6>(src, dst, d, taps, odd_rule, st, pk, plan);
+    case 8: return fused_analysis_mode<ND, 8>(src, dst, d, taps, odd_rule, st, pk, plan);
+    case 10: return fused_analysis_mode<ND, 10>(src, dst, d, taps, odd_rule, st, pk, plan);
     default: return false;
   }
 }
-bool dwt_fused_analysis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk) {
-  return d->nd == 3 ? fused_analysis_nd<3>(src, dst, d, taps, odd_rule, st, pk) : fused_analysis_nd<2>(src, dst, d, taps, odd_rule, st, pk);
+bool dwt_fused_analysis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk,
+                        wdno_dwt_plan* plan) {
+  return d->nd == 3 ? fused_analysis_nd<3>(src, dst, d, taps, odd_rule, st, pk, plan) : fused_analysis_nd<2>(src, dst, d, taps, odd_rule, st, pk, plan);
 }

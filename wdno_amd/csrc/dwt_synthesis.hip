@@ -1,7 +1,6 @@
 // dwt_synthesis.hip -- the fused single-launch synthesis kernels (packed coefficients -> 2-D / 3-D signal) and the choice among them; the
 // scheme of the fused transforms and the steps the kernels share are in dwt_tiles.h, the per-axis reference in dwt.hip.
 #include "dwt_tiles.h"
-#include <type_traits>
 #include <algorithm>
 
 // q = (n + off) >> 1, r = (n + off) & 1: x[n] = sum_i lo[q - i] g_lo[r + 2 i] + hi[q - i] g_hi[r + 2 i], i < L/2.
@@ -453,9 +452,10 @@ __global__ __launch_bounds__(256) void dwt_synthesis3_stream_kernel(const float*
   }
 }
 
+// decide: the tile geometry and the kernel of a synthesis, nothing launched. false = not covered by a fused kernel.
 template <int ND, int L, int MODE>
-static bool fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, hipStream_t st) {
-  FusedGeom g = dw_geom(d, L, MODE);
+static bool synthesis_decide(const wdno_dwt_desc* d, FusedGeom& g, FusedChoice& c) {
+  g = dw_geom(d, L, MODE);
   constexpr int E = L / 2 - 1;
   auto qcount = [&](int N) { return ((N - 1 + g.off) >> 1) - (g.off >> 1) + 1; };
   g.qt0 = g.qh0 = g.qw0 = g.off >> 1;
@@ -463,12 +463,14 @@ static bool fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d
   g.QT = qcount(g.T);
   g.FW = 2 * qcount(g.W);
   if (g.cs_img >= (1ll << 31) || (int64_t)g.T * g.H * g.W >= (1ll << 31)) return false;      // 32-bit offsets within an image
-  constexpr int NQ = (ND == 3) ? 4 : 4;
+  constexpr int NQ = 4;
   size_t lds;
   if (ND == 3 && wdno_debug_mode != WDNO_DBG_DWT3_SYNTH_LDS) {
-    // streaming kernel: q-rows per tile from the register budget (ITEMS columns of 2 NQ samples per thread) and a 32 KB LDS budget
-    auto stream = [&](auto ITEMS_C, auto NQ_C) -> bool {
-      constexpr int ITEMS = decltype(ITEMS_C)::value, NQS = decltype(NQ_C)::value;
+    // streaming kernel: q-rows per tile from the register budget (ITEMS columns of 2 NQ samples per thread) and a 32 KB LDS budget.
+    // tile shape: 2 columns per thread, NQ = 4 q-frames per tile. Measured on [32,8,18,34,34] / [10,8,34,66,66] with this kernel (us):
+    // 2 col NQ 4: 16.1 / 33.3; 3 col: 17.2 / 42.0; 4 col: 19.7 / 37.4; 2 col NQ 8: 17.8 / 31.8; 3 col NQ 8: 21.5 / 47.1
+    auto stream = [&]() -> bool {
+      constexpr int ITEMS = 2;
       const int NW = g.FW;
       int nqh = (ITEMS * 256) / (2 * NW);
       const int lds_rows = (int)(dwt_fused_lds_budget(32) / ((size_t)NW * sizeof(float)));      // 4 (NQH + E) + 4 NQH rows of NW floats
@@ -478,7 +480,7 @@ static bool fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d
       const int tiles = cdiv(g.QH, nqh);
       g.NH = cdiv(g.QH, tiles);
       g.tiles_h = tiles;
-      g.tiles_t = cdiv(g.QT, NQS);
+      g.tiles_t = cdiv(g.QT, NQ);
       const size_t lds = (size_t)dw_stream_lds<2>(NW, g.NH + E, g.NH) * sizeof(float);
       const int64_t nbs = (int64_t)g.n_img * g.tiles_t * g.tiles_h;
       const int n_w = 4 * (g.NH + E) * (NW / 2);               // W-pass items of a frame: WMAX per thread, held in registers
@@ -486,15 +488,13 @@ static bool fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d
       g.n_blocks = (int)nbs;
       g.dFW = make_fastdiv(NW); g.dQW = make_fastdiv(NW / 2); g.dEH = make_fastdiv(g.NH + E); g.dNQH2 = make_fastdiv(2 * g.NH);
       g.debug = 0;
-      if (n_w <= 4 * 256) dwt_synthesis3_stream_kernel<L, MODE, NQS, ITEMS, 4><<<(int)nbs, 256, lds, st>>>(src, dst, g, taps);
-      else dwt_synthesis3_stream_kernel<L, MODE, NQS, ITEMS, 8><<<(int)nbs, 256, lds, st>>>(src, dst, g, taps);
+      c = FusedChoice{WDNO_DWT_SYNTHESIS3_STREAM, n_w <= 4 * 256 ? 4 : 8, lds};
       return true;
     };
-    // tile shape: 2 columns per thread, NQ = 4 q-frames per tile. Measured on [32,8,18,34,34] / [10,8,34,66,66] with this kernel (us):
-    // 2 col NQ 4: 16.1 / 33.3; 3 col: 17.2 / 42.0; 4 col: 19.7 / 37.4; 2 col NQ 8: 17.8 / 31.8; 3 col NQ 8: 21.5 / 47.1
-    const bool ok = stream(std::integral_constant<int, 2>{}, std::integral_constant<int, NQ>{});
-    if (ok) return true;
+    if (stream()) return true;
   }
+  const int RW = dw_staged_row_width((g.FW / 2 + 3) / 4, L);
+  bool staged = false;
   if (ND == 3) {
     // floats: 2 ET NW (2 EH + 2 NQH), EH = NQH + E
     const size_t per_row = (size_t)2 * (NQ + E) * g.FW * sizeof(float);
@@ -513,42 +513,64 @@ static bool fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d
     g.NH = (int)nq_max;                                       // NH + E <= 2 NQ + E <= 16: the staged W pass keeps one register per row of a wave
     g.tiles_h = cdiv(g.QH, g.NH);
     g.tiles_t = 1;
-    // S1 + the staged raw rows of dwt_synthesis2_kernel -- also what the launch of dwt_synthesis_fused_kernel<2, ..> below asks for, which has
-    // no staged rows: more than that kernel's dw_synthesis_lds, kept as it was (profiles/dwt_tiles_header.md, "seen while reading")
-    lds = (size_t)dw_synthesis2_lds<2>(g.FW, g.NH + E, dw_staged_row_width((g.FW / 2 + 3) / 4, L)) * sizeof(float);
+    // dwt_synthesis2_kernel: S1 + its staged raw rows. Rows too wide to stage (RW > 256) go to dwt_synthesis_fused_kernel<2, ..>, which has
+    // S1 alone (asking for the staged rows there as well went past 64 KB from W = 520 on, L = 10)
+    staged = g.NH + E <= 2 * NQ + E && RW <= 256;
+    lds = staged ? (size_t)dw_synthesis2_lds<2>(g.FW, g.NH + E, RW) * sizeof(float) : per_row * (size_t)(g.NH + E);
   }
   const int64_t nb = (int64_t)g.n_img * g.tiles_t * g.tiles_h;
   if (nb > 0x7fffffff) return false;
   g.n_blocks = (int)nb;
   g.dFW = make_fastdiv(g.FW); g.dQW = make_fastdiv(g.FW / 2); g.dEH = make_fastdiv(g.NH + E); g.dNQH2 = make_fastdiv(2 * g.NH);
-  const int RW = dw_staged_row_width((g.FW / 2 + 3) / 4, L);
   g.dQW4 = make_fastdiv((g.FW / 2 + 3) / 4); g.dRW = make_fastdiv(RW);
   g.debug = wdno_debug_mode;
-  if (ND == 2) {
-    if (g.NH + E <= 2 * NQ + E && RW <= 256) {
-      const int grid = (int)nb;
-      if (RW <= 128) dwt_synthesis2_kernel<L, MODE, NQ, 1><<<grid, 256, lds, st>>>(src, dst, g, taps);
-      else dwt_synthesis2_kernel<L, MODE, NQ, 2><<<grid, 256, lds, st>>>(src, dst, g, taps);
-      return true;
-    }
+  if (staged) {
+    c = FusedChoice{WDNO_DWT_SYNTHESIS2, RW <= 128 ? 1 : 2, lds};
+    return true;
   }
   if ((int64_t)2 * (NQ + E) * 2 * (g.NH + E) * g.FW * (int64_t)std::max(g.FW, 2 * (g.NH + E)) >= (1ll << 32)) return false;   // fd_div range
-  dwt_synthesis_fused_kernel<ND, L, MODE, NQ><<<(int)nb, 256, lds, st>>>(src, dst, g, taps);
+  c = FusedChoice{WDNO_DWT_SYNTHESIS_FUSED, 0, lds};
+  return true;
+}
+
+// launch: what synthesis_decide chose
+template <int ND, int L, int MODE>
+static void synthesis_launch(const FusedChoice& c, const float* src, float* dst, const FusedGeom& g, const Taps& taps, hipStream_t st) {
+  constexpr int NQ = 4;
+  const int nb = g.n_blocks;
+  if (c.family == WDNO_DWT_SYNTHESIS3_STREAM) {
+    if (c.variant == 4) dwt_synthesis3_stream_kernel<L, MODE, NQ, 2, 4><<<nb, 256, c.lds, st>>>(src, dst, g, taps);
+    else dwt_synthesis3_stream_kernel<L, MODE, NQ, 2, 8><<<nb, 256, c.lds, st>>>(src, dst, g, taps);
+  } else if (c.family == WDNO_DWT_SYNTHESIS2) {
+    if (c.variant == 1) dwt_synthesis2_kernel<L, MODE, NQ, 1><<<nb, 256, c.lds, st>>>(src, dst, g, taps);
+    else dwt_synthesis2_kernel<L, MODE, NQ, 2><<<nb, 256, c.lds, st>>>(src, dst, g, taps);
+  } else {
+    dwt_synthesis_fused_kernel<ND, L, MODE, NQ><<<nb, 256, c.lds, st>>>(src, dst, g, taps);
+  }
+}
+
+template <int ND, int L, int MODE>
+static bool fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, hipStream_t st, wdno_dwt_plan* plan) {
+  FusedGeom g;
+  FusedChoice c;
+  if (!synthesis_decide<ND, L, MODE>(d, g, c)) return false;
+  if (plan) dw_plan_of(g, c, plan);
+  else synthesis_launch<ND, L, MODE>(c, src, dst, g, taps, st);
   return true;
 }
 
 template <int ND>
-static bool fused_synthesis_nd(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, hipStream_t st) {
+static bool fused_synthesis_nd(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, hipStream_t st, wdno_dwt_plan* plan) {
   const bool zero = d->mode == 1;
   switch (d->L) {
-    case 2: return zero ? fused_synthesis<ND, 2, 1>(src, dst, d, taps, st) : fused_synthesis<ND, 2, 0>(src, dst, d, taps, st);
-    case 4: return zero ? fused_synthesis<ND, 4, 1>(src, dst, d, taps, st) : fused_synthesis<ND, 4, 0>(src, dst, d, taps, st);
-    case 6: return zero ? fused_synthesis<ND, 6, 1>(src, dst, d, taps, st) : fused_synthesis<ND, 6, 0>(src, dst, d, taps, st);
-    case 8: return zero ? fused_synthesis<ND, 8, 1>(src, dst, d, taps, st) : fused_synthesis<ND, 8, 0>(src, dst, d, taps, st);
-    case 10: return zero ? fused_synthesis<ND, 10, 1>(src, dst, d, taps, st) : fused_synthesis<ND, 10, 0>(src, dst, d, taps, st);
+    case 2: return zero ? fused_synthesis<ND, 2, 1>(src, dst, d, taps, st, plan) : fused_synthesis<ND, 2, 0>(src, dst, d, taps, st, plan);
+    case 4: return zero ? fused_synthesis<ND, 4, 1>(src, dst, d, taps, st, plan) : fused_synthesis<ND, 4, 0>(src, dst, d, taps, st, plan);
+    case 6: return zero ? fused_synthesis<ND, 6, 1>(src, dst, d, taps, st, plan) : fused_synthesis<ND, 6, 0>(src, dst, d, taps, st, plan);
+    case 8: return zero ? fused_synthesis<ND, 8, 1>(src, dst, d, taps, st, plan) : fused_synthesis<ND, 8, 0>(src, dst, d, taps, st, plan);
+    case 10: return zero ? fused_synthesis<ND, 10, 1>(src, dst, d, taps, st, plan) : fused_synthesis<ND, 10, 0>(src, dst, d, taps, st, plan);
     default: return false;
   }
 }
-bool dwt_fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, hipStream_t st) {
-  return d->nd == 3 ? fused_synthesis_nd<3>(src, dst, d, taps, st) : fused_synthesis_nd<2>(src, dst, d, taps, st);
+bool dwt_fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, hipStream_t st, wdno_dwt_plan* plan) {
+  return d->nd == 3 ? fused_synthesis_nd<3>(src, dst, d, taps, st, plan) : fused_synthesis_nd<2>(src, dst, d, taps, st, plan);
 }

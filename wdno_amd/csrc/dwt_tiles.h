@@ -47,9 +47,20 @@ struct FusedGeom {
 
 struct PackedStore { int img_inner, row_w; int64_t cs_outer; const float* resc; };     // wdno_dwt_fwd_packed
 
-// The two fused units, one entry each (fused_try of dwt.hip): true = the transform was launched as ONE fused kernel, false = not covered.
-bool dwt_fused_analysis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk);
-bool dwt_fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, hipStream_t st);
+// What a chooser decided: the kernel (WDNO_DWT_* of wdno_hip.h), its variant (PMAX of dwt_synthesis2_kernel, WMAX of the stream kernel, 0
+// otherwise) and the dynamic LDS of the launch; the tile geometry is the FusedGeom next to it. Each unit has ONE "decide" function, which
+// fills both and launches nothing, and one "launch" function, which only reads them.
+struct FusedChoice { int family, variant; size_t lds; };
+static inline void dw_plan_of(const FusedGeom& g, const FusedChoice& c, wdno_dwt_plan* out) {
+  *out = wdno_dwt_plan{c.family, c.variant, g.NH, g.tiles_h, g.tiles_t, g.n_blocks, (int)c.lds, WDNO_OK};
+}
+
+// The two fused units, one entry each (fused_try of dwt.hip): true = the transform is covered by ONE fused kernel, false = not covered.
+// plan == nullptr: decide and launch. plan != nullptr (wdno_dwt_plan_query): decide only -- *plan receives the decision, nothing is launched
+// and src / dst are not touched.
+bool dwt_fused_analysis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, bool odd_rule, hipStream_t st, const PackedStore* pk,
+                        wdno_dwt_plan* plan);
+bool dwt_fused_synthesis(const float* src, float* dst, const wdno_dwt_desc* d, const Taps& taps, hipStream_t st, wdno_dwt_plan* plan);
 // LDS budget per block (dwt.hip; <= 64 KB: the default dynamic-LDS limit, no function attribute needed -> graph-capture safe). Smaller
 // tiles = more blocks per CU to hide the latency of the global reads, at the price of more halo re-reads through L2.
 size_t dwt_fused_lds_budget(long default_kb);

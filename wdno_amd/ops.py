@@ -2346,6 +2346,18 @@ def dwt_call(kind, src, dst, nd, mode, filters, n_img, in_dims, out_dims, cs):
     _lib.check(fn(_p(src), _p(dst), C.byref(d), fl, _p(ws), nb, _stream()), 'dwt_' + kind)
 
 
+def dwt_plan(kind, nd, mode, L, n_img, in_dims, out_dims, cs):
+    """What dwt_call(kind, ...) launches for this descriptor (csrc/dwt.hip: wdno_dwt_plan_query; kind also 'fwd_packed'): dict(family 'per_axis' |
+    'analysis' | 'analysis_packed' | 'synthesis2' | 'synthesis_fused' | 'synthesis3_stream' (None when rc != 0), variant, nh, tiles_h, tiles_t,
+    blocks, lds_bytes, rc). Follows the debug mode and WDNO_DWT_LDS_KB as the launch does. No launch, no device needed."""
+    d = _dwt_desc(nd, mode, L, n_img, in_dims, out_dims, cs)
+    pl = _lib.DwtPlan()
+    _lib.check(_lib_().wdno_dwt_plan_query(C.byref(d), _lib.DWT_ENTRIES.index(kind), C.byref(pl)), 'dwt_plan')
+    out = _plan_dict(pl)
+    out['family'] = _lib.DWT_FAMILIES[pl.family] if pl.family >= 0 else None
+    return out
+
+
 def upsample_coef_raw(x, outer, a, mid, b, c, fa, fb, fc):
     x = _chk(x, 'coef')
     out = torch.empty((outer * a * fa * mid * b * fb * c * fc,), device=x.device, dtype=torch.float32)
