@@ -1,4 +1,4 @@
-"""The layer-by-layer attention kernels (csrc/attention.hip, csrc/linattn.hip) and the channel LayerNorm (csrc/norm.hip) in plain torch on the CPU, fp64, forward
+"""The layer-by-layer attention kernels (csrc/attention.hip, csrc/linattn.hip) and the channel LayerNorm (csrc/layernorm.hip) in plain torch on the CPU, fp64, forward
 and hand-written backward (no autograd), with an ERROR SCALE per output, built stage by stage as tests/attn_ref.py's docstring describes. Test
 infrastructure only. Unlike attn_ref these start from a GIVEN qkv / x (exact fp32 inputs): no LayerNorm or projection in front, so a stage's
 scale starts from the rounding of its own terms:
@@ -531,7 +531,7 @@ LN_C = (4, 8, 12, 16, 32, 36, 64, 96, 128, 256, 260, 512, 516, 1024)      # 32: 
 
 
 def ln_shape(c):
-    """(threads per row, float4 per lane) of csrc/norm.hip's ln_shape, for the cases' row counts; the GPU test asserts them from the plan"""
+    """(threads per row, float4 per lane) of csrc/layernorm.hip's ln_shape, for the cases' row counts; the GPU test asserts them from the plan"""
     c4 = c // 4
     p2 = lambda v: 1 << (v - 1).bit_length()
     return (max(p2(c4), 2), 1) if c4 <= 64 else (64, p2(-(-c4 // 64)))

@@ -1,4 +1,4 @@
-"""The layer-by-layer attention kernels (csrc/attention.hip, csrc/linattn.hip) and the channel LayerNorm (csrc/norm.hip) held ELEMENT BY ELEMENT to the fp64
+"""The layer-by-layer attention kernels (csrc/attention.hip, csrc/linattn.hip) and the channel LayerNorm (csrc/layernorm.hip) held ELEMENT BY ELEMENT to the fp64
 references of tests/attn_kernels_ref.py, |got - ref| <= K 2^-24 scale + flush, on a case matrix that visits every launch regime the plan queries
 (ops.attn_plan, ops.linattn_plan, ops.layernorm_plan) can report: every kernel family, one item up to a grid-stride walk with a second pass, the
 bias-gradient partial in registers and in LDS, every chunk count edge of the linear attention, every (lanes per row, vectors per lane) pair of the

@@ -28,16 +28,26 @@ def ops():
 @pytest.mark.parametrize('case,nchunk,rows', [c[:3] for c in R.CASES], ids=[R.case_id((c[0], 'std')) for c in R.CASES])
 def test_case_reaches_its_regime(ops, case, nchunk, rows):
     """nchunk (from the workspace size: ws = 16 N nchunk C + 16 N C + 16 N G + 64 bytes) and the rows of column-sum partials of the planes
-    backward (N x blocks per sample) are what the case was chosen for; a retune of the heuristics has to revisit the matrix."""
+    backward (N x blocks per sample) are what the case was chosen for; a retune of the heuristics has to revisit the matrix.
+    And the tail the planes forms carve out of their workspace -- from the next 64-byte boundary behind the plain workspace: forward the
+    per-chunk maxima (N x nchunk x 2 floats), backward N x CAP rows of C fp64 column-sum partials and the maxima behind them -- fits the size
+    the library asks for."""
     lib = ops._lib_()
     n, s, c, g = case
-    num = int(lib.wdno_groupnorm_ws_bytes(n, s, c, g)) - 16 * n * c - 16 * n * g - 64
+    ws = int(lib.wdno_groupnorm_ws_bytes(n, s, c, g))
+    num = ws - 16 * n * c - 16 * n * g - 64
     assert num % (16 * n * c) == 0 and num // (16 * n * c) == nchunk, (num / (16 * n * c), nchunk)
     off, prow = C.c_size_t(0), C.c_int(0)
     assert lib.wdno_groupnorm_bwd_planes_tail(n, s, c, g, C.byref(off), C.byref(prow)) == 0
     if rows is not None:
         assert prow.value == rows, (prow.value, rows)
     assert R.planes_ok(c) == (rows is not None)
+    CAP = 128                                             # blocks per sample of the planes backward at the most
+    align64 = lambda b: (b + 63) // 64 * 64
+    assert off.value == align64(ws), (off.value, ws)
+    assert off.value + n * CAP * c * 8 + n * nchunk * 2 * 4 <= int(lib.wdno_groupnorm_bwd_planes_ws_bytes(n, s, c, g))
+    assert prow.value <= n * CAP, (prow.value, n * CAP)
+    assert align64(ws) + n * nchunk * 2 * 4 <= int(lib.wdno_groupnorm_fwd_planes_ws_bytes(n, s, c, g))
 
 
 def _dev(t, grad=False):

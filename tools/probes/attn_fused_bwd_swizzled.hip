@@ -173,7 +173,7 @@ __device__ __forceinline__ void tb_split16(const f32x16& v, float s, half8 (&h)[
     }
   }
 }
-// LayerNorm of one row by its 16 lanes (norm.hip: layernorm_kernel), planes written, mean and 1/std returned
+// LayerNorm of one row by its 16 lanes (layernorm.hip: layernorm_kernel), planes written, mean and 1/std returned
 __device__ __forceinline__ void tb_ln_row(float4 xv, float4 g, float eps, float ps, _Float16* __restrict__ Ah, _Float16* __restrict__ Al, int row, int c4,
                                           float& mean, float& rstd) {
   mean = tf_row16_sum((xv.x + xv.y) + (xv.z + xv.w)) * (1.0f / TF_C);

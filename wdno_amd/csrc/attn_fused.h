@@ -186,7 +186,7 @@ __device__ __forceinline__ void tf_fit(float& sc, float amax, f32x16& w0, f32x16
 // mean and 1/std handed back (the backward kernels keep them)
 __device__ __forceinline__ void tf_ln_row(float4 xv, float4 g, float eps, float ps, _Float16* __restrict__ Ah, _Float16* __restrict__ Al, int row, int c4,
                                           float& mean, float& rstd) {
-  // norm.hip's layernorm_kernel (two-pass mean / variance over the 16 lanes of the row), the lane sums taken in DPP order
+  // layernorm.hip's layernorm_kernel (two-pass mean / variance over the 16 lanes of the row), the lane sums taken in DPP order
   mean = tf_row16_sum((xv.x + xv.y) + (xv.z + xv.w)) * (1.0f / TF_C);
   xv.x -= mean; xv.y -= mean; xv.z -= mean; xv.w -= mean;
   const float var = tf_row16_sum((xv.x * xv.x + xv.y * xv.y) + (xv.z * xv.z + xv.w * xv.w)) * (1.0f / TF_C);

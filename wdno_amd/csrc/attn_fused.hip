@@ -9,7 +9,7 @@
 //
 // One block = four waves = the four heads of ONE sequence at a time; blocks walk sequences with a grid stride, two blocks per CU.
 //   * LayerNorm by the whole block (16 lanes per row), result split into fp16 (hi, lo) planes in LDS [32 tokens][64] (rows 24..31 zero;
-//     row pitch 144 B = conflict-free ds_read_b128 fragments). Plane scale from the bound |LN| <= sqrt(C) max|g| (as norm.hip does).
+//     row pitch 144 B = conflict-free ds_read_b128 fragments). Plane scale from the bound |LN| <= sqrt(C) max|g| (as layernorm.hip does).
 //   * Projection on v_mfma_f32_32x32x16_f16 with the three products hi*lo + lo*hi + hi*hi (the fp32-equivalent arithmetic of the
 //     convolutions, conv_h3t.hip): A = the head's 96 rows of the packed W_qkv planes, held in registers for the whole kernel
 //     (24 fragments), B = the token planes. Accumulators come out as [feature][token]: a lane owns one token and the features

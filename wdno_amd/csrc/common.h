@@ -27,6 +27,7 @@ int wdno_num_cus();
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 // memory-bound kernels: cap the grid and grid-stride the rest (256 CUs x 8 blocks)
 static inline int stream_grid(int64_t work_items, int block) {

@@ -1612,6 +1612,12 @@ def _claim_grad_slot(t):
     return slot
 
 
+def _gn_planes_ok(c):
+    """The channel counts the GroupNorm planes kernels take (csrc/norm.hip: gn_planes_ok): C / 8 a power of two <= 256."""
+    c8 = c // 8
+    return c % 8 == 0 and c8 <= 256 and (c8 & (c8 - 1)) == 0
+
+
 class _GroupNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, ss, groups, act_silu, eps, out_planes=False):
@@ -1626,8 +1632,7 @@ class _GroupNormAct(torch.autograd.Function):
         stats = torch.empty((lib.wdno_groupnorm_stats_floats(n, c, groups),), device=x.device, dtype=torch.float32)      # (mean, rstd) + the affine tables the backward reads
         ssc = None if ss is None else _chk(ss, 'scale_shift')
         ctx.ss_slot = _claim_grad_slot(ss) if ssc is ss else None      # (ops.linear_multi: d(scale_shift) goes straight into its buffer)
-        c8_ = c // 8
-        if out_planes and CONV_MATH in ('f16x3', 'bf16') and c % 8 == 0 and c8_ <= 256 and (c8_ & (c8_ - 1)) == 0:
+        if out_planes and CONV_MATH in ('f16x3', 'bf16') and _gn_planes_ok(c):
             nbp = lib.wdno_groupnorm_fwd_planes_ws_bytes(n, s, c, groups)
             wsp = _ws(nbp, x.device)
             hi = torch.empty((n * s, c), device=x.device, dtype=torch.float16)
@@ -1654,9 +1659,7 @@ class _GroupNormAct(torch.autograd.Function):
         ctx.meta = (n, s, c, groups, int(act_silu))
         ctx.epoch = _param_epoch(gamma)
         # the convolution that produced x takes its dy as fp16 planes (conv_cl(..., grad_planes=True)): deliver dx in that form
-        c8 = c // 8
-        ctx.grad_planes = (GRAD_PLANES and getattr(x_in, '_wdno_grad_planes', False) and CONV_MATH in ('f16x3', 'bf16') and c % 8 == 0
-                           and c8 <= 256 and (c8 & (c8 - 1)) == 0)
+        ctx.grad_planes = GRAD_PLANES and getattr(x_in, '_wdno_grad_planes', False) and CONV_MATH in ('f16x3', 'bf16') and _gn_planes_ok(c)
         return _leave_amax(y, rec)
 
     @staticmethod
@@ -1751,9 +1754,7 @@ class _GroupNormActAdd(torch.autograd.Function):
         ctx.save_for_backward(x, gamma, beta, ssc, stats)
         ctx.meta = (n, s, c, groups, int(act_silu))
         ctx.epoch = _param_epoch(gamma)
-        c8 = c // 8
-        ctx.grad_planes = (GRAD_PLANES and getattr(x_in, '_wdno_grad_planes', False) and CONV_MATH in ('f16x3', 'bf16') and c % 8 == 0
-                           and c8 <= 256 and (c8 & (c8 - 1)) == 0)
+        ctx.grad_planes = GRAD_PLANES and getattr(x_in, '_wdno_grad_planes', False) and CONV_MATH in ('f16x3', 'bf16') and _gn_planes_ok(c)
         return _leave_amax(y, yrec)
 
     @staticmethod
@@ -1764,9 +1765,7 @@ class _GroupNormActAdd(torch.autograd.Function):
 
 def groupnorm_act_add(x, gamma, beta, groups, residual, scale_shift=None, act=True, eps=1e-5):
     """act(GroupNorm(x)) + residual: the tail of a ResnetBlock whose skip is the identity."""
-    c = x.shape[-1]
-    c8 = c // 8
-    if not (c % 8 == 0 and c8 <= 256 and (c8 & (c8 - 1)) == 0 and x.shape == residual.shape):
+    if not (_gn_planes_ok(x.shape[-1]) and x.shape == residual.shape):
         return add(groupnorm_act(x, gamma, beta, groups, scale_shift, act, eps), residual)
     return _GroupNormActAdd.apply(x, gamma, beta, scale_shift, residual, groups, act, eps)
 
