@@ -121,6 +121,23 @@ int wdno_pack_smoke_state(const float* coef, int64_t coef_sim_stride, const floa
 int wdno_pack_smoke_fields(const float* coef, int64_t coef_sim_stride, const float* rho0, int64_t rho0_sim_stride, const float* curve,
                            int64_t curve_sim_stride, const float* dec_lo_host, const float* dec_hi_host, int L, const float* rescaler,
                            float* state, int64_t B, int F, int nt, int nx, int pad_t, int pad_x, int H0, int W0, int T0, wdno_stream_t s);
+/* The two-level state of the super-resolution models for a batch, one launch (Smoke_wave.__getitem__ with is_super_model):
+ *   state[b][f][c][h][w] = value / rescaler[c],   state [B][pad_t][16 F + 2][pad_x][pad_x]; everything not listed is 0
+ *   c <  8 F          : fine (level l, [.][F][8][nt][nx][nx]) with one replicated border coefficient
+ *                       time : fine[c][clamp(f - 1, 0, nt - 1)][h][w]                                  for f < nt + 2, h, w < nx
+ *                       space: fine[c][f][clamp(h - 1, 0, nx - 1)][clamp(w - 1, 0, nx - 1)]            for f < nt, h, w < nx + 2
+ *   8 F <= c < 16 F   : coarse (level l + 1, [.][F][8][nt_c][nx_c][nx_c]), nearest x2 (upsample_coef), cc = c - 8 F
+ *                       time : coarse[cc][f >> 1][h][w]                                                for f < nt + 2, h, w < nx
+ *                       space: coarse[cc][f][h >> 1][w >> 1]                                           for f < nt, h, w < nx + 2
+ *   c == 16 F, 16 F + 1: the two condition channels of wdno_pack_smoke_state, from level l, without the border offset
+ * sim = idx[b] (NULL: b) and the per-simulation strides as in wdno_pack_smoke_state. IEEE division: bit-identical to the torch formulation.
+ * WDNO_EINVAL unless (time) nt + 2 == 2 nt_c, nx_c == nx, nt + 2 <= pad_t, nx <= pad_x / (space) nx + 2 == 2 nx_c, nt_c == nt, nx + 2 <= pad_x,
+ * nt <= pad_t, and for another `kind`; WDNO_EUNSUPPORTED unless pad_t % 4 == 0 and pad_x % 4 == 0. Nothing is launched then. */
+enum { WDNO_PACK_SUPER_TIME = 0, WDNO_PACK_SUPER_SPACE = 1 };
+int wdno_pack_smoke_super_state(const float* fine, int64_t fine_sim_stride, const float* coarse, int64_t coarse_sim_stride,
+                                const float* init_coef, int64_t init_sim_stride, const float* smokeout, int64_t so_sim_stride,
+                                const int64_t* idx, const float* rescaler, float* state, int64_t B, int F, int nt, int nx, int nt_c,
+                                int nx_c, int kind, int pad_t, int pad_x, wdno_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------ layout
  * API layout [N, C, S] (S = product of spatial dims) <-> channels-last [N, S, Cp] (Cp >= C, zero padded). */

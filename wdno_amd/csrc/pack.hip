@@ -182,6 +182,116 @@ extern "C" int wdno_pack_smoke_state(const float* coef, int64_t coef_sim_stride,
   return wdno_check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------ two-level states (super-resolution models)
+// Smoke_wave.__getitem__ with is_super_model (data_2d.py:186-200): the 8 F channels of level l carrying one replicated border coefficient in
+// time (KIND 0: frame clamp(f - 1)) or in space (KIND 1: row / column clamp(. - 1)), 8 F more with level l + 1 nearest-upsampled x2 on the same
+// axes (upsample_coef), then the two condition channels of the base kernel, without the border offset. The box of the 16 F channels is
+// [bt][bx][bx], bt = nt + 2 = 2 nt_c / bx = nx (time), bt = nt / bx = nx + 2 = 2 nx_c (space): every clamped or halved index stays inside its store.
+struct PackSuperP {
+  const float* fine; const float* coarse; const float* init; const float* so; const int64_t* idx; const float* resc; float* out;
+  int64_t fine_sim, coarse_sim, init_sim, so_sim;      // elements between consecutive simulations in the four stores
+  int F, nt, nx, nt_c, nx_c, pad_t, pad_x, C;
+  FastDiv dW4, dPX;
+};
+
+// four consecutive floats of a row of n from src (w0 = their column): 8-byte loads where `even` says the address is a multiple of 8 bytes
+__device__ __forceinline__ void pk_row4(const float* __restrict__ src, int w0, int n, bool even, float* v) {
+  if (w0 + 3 < n && even) {
+    const float2 a = reinterpret_cast<const float2*>(src)[0], bb = reinterpret_cast<const float2*>(src)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = bb.x; v[3] = bb.y;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (w0 + e < n) v[e] = src[e];
+  }
+}
+
+// Same decomposition as pack_smoke_state_kernel: grid = (B * pad_t, blocks per frame), a block works inside ONE frame of one sample.
+// Space mode reads the fine rows shifted by one column: four dword loads per float4, neighbouring lanes on neighbouring addresses (the row is
+// re-read from L2 by the lanes of one wave only); one coarse pair feeds the float4, the rows h and h + 1 of the 2 x 2 patch read it again from L2.
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_smoke_super_kernel(PackSuperP p) {
+  constexpr bool SPACE = KIND != 0;
+  const unsigned W4 = (unsigned)p.pad_x >> 2, stride = gridDim.y * 256u;
+  const int rep = p.pad_t >> 2, half = p.pad_x >> 1, C8 = 8 * p.F;
+  const int bt = SPACE ? p.nt : p.nt + 2, bx = SPACE ? p.nx + 2 : p.nx;
+  const unsigned fstride4 = (unsigned)p.C * (unsigned)p.pad_x * W4;
+  const int b = (int)(blockIdx.x / (unsigned)p.pad_t), f = (int)(blockIdx.x - (unsigned)b * (unsigned)p.pad_t);
+  const int64_t sim = p.idx ? p.idx[b] : b;
+  const bool fine_even = !(p.nx & 1) && !(p.fine_sim & 1), coarse_even = !(p.nx_c & 1) && !(p.coarse_sim & 1);
+  float4* __restrict__ out = reinterpret_cast<float4*>(p.out) + (size_t)blockIdx.x * fstride4;
+  for (unsigned i = blockIdx.y * 256u + threadIdx.x; i < fstride4; i += stride) {
+    unsigned q = fd_div(i, p.dW4);
+    const int w0 = (int)(i - q * W4) * 4;
+    const unsigned cq = fd_div(q, p.dPX);
+    const int h = (int)(q - cq * (unsigned)p.pad_x), c = (int)cq;
+    const float r = p.resc[c];
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c < 2 * C8) {
+      if (f < bt && h < bx) {
+        if (c < C8) {
+          if (!SPACE) {
+            const int fs = min(max(f - 1, 0), p.nt - 1);
+            pk_row4(p.fine + sim * p.fine_sim + (((int64_t)c * p.nt + fs) * p.nx + h) * p.nx + w0, w0, p.nx, fine_even, v);
+          } else {
+            const int hs = min(max(h - 1, 0), p.nx - 1);
+            const float* src = p.fine + sim * p.fine_sim + (((int64_t)c * p.nt + f) * p.nx + hs) * p.nx;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (w0 + e < bx) v[e] = src[min(max(w0 + e - 1, 0), p.nx - 1)];
+          }
+        } else {
+          const int cc = c - C8;
+          if (!SPACE) {
+            pk_row4(p.coarse + sim * p.coarse_sim + (((int64_t)cc * p.nt_c + (f >> 1)) * p.nx_c + h) * p.nx_c + w0, w0, p.nx_c, coarse_even, v);
+          } else {
+            const int j = w0 >> 1;                                         // (w0 a multiple of 4: j even)
+            const float* src = p.coarse + sim * p.coarse_sim + (((int64_t)cc * p.nt_c + f) * p.nx_c + (h >> 1)) * p.nx_c + j;
+            if (j + 1 < p.nx_c && coarse_even) {
+              const float2 a = reinterpret_cast<const float2*>(src)[0];
+              v[0] = v[1] = a.x; v[2] = v[3] = a.y;
+            } else {
+              if (j < p.nx_c) v[0] = v[1] = src[0];
+              if (j + 1 < p.nx_c) v[2] = v[3] = src[1];
+            }
+          }
+        }
+      }
+    } else if (c == 2 * C8) {
+      if (h < p.nx) {
+        const float* src = p.init + sim * p.init_sim + ((int64_t)(f / rep) * p.nx + h) * p.nx;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (w0 + e < p.nx) v[e] = src[w0 + e];
+      }
+    } else if (f < p.nt) {
+      const float s = p.so[sim * p.so_sim + (int64_t)(h >= half ? 1 : 0) * p.nt + f];
+      v[0] = v[1] = v[2] = v[3] = s;
+    }
+    out[i] = make_float4(v[0] / r, v[1] / r, v[2] / r, v[3] / r);
+  }
+}
+
+extern "C" int wdno_pack_smoke_super_state(const float* fine, int64_t fine_sim_stride, const float* coarse, int64_t coarse_sim_stride,
+                                           const float* init_coef, int64_t init_sim_stride, const float* smokeout, int64_t so_sim_stride,
+                                           const int64_t* idx, const float* rescaler, float* state, int64_t B, int F, int nt, int nx, int nt_c,
+                                           int nx_c, int kind, int pad_t, int pad_x, wdno_stream_t s) {
+  WDNO_REQUIRE(fine && coarse && init_coef && smokeout && rescaler && state && B > 0 && F > 0 && nt > 0 && nx > 0 && nt_c > 0 && nx_c > 0);
+  WDNO_REQUIRE(kind == WDNO_PACK_SUPER_TIME || kind == WDNO_PACK_SUPER_SPACE);
+  if (kind == WDNO_PACK_SUPER_TIME) WDNO_REQUIRE(nt + 2 == 2 * nt_c && nx_c == nx && nt + 2 <= pad_t && nx <= pad_x);
+  else WDNO_REQUIRE(nx + 2 == 2 * nx_c && nt_c == nt && nx + 2 <= pad_x && nt <= pad_t);
+  WDNO_REQUIRE(fine_sim_stride >= (int64_t)F * 8 * nt * nx * nx && coarse_sim_stride >= (int64_t)F * 8 * nt_c * nx_c * nx_c &&
+               init_sim_stride >= 4ll * nx * nx && so_sim_stride >= 2ll * nt);
+  const int C = 16 * F + 2;
+  int rc = pk_check(B, pad_t, pad_x, C);
+  if (rc) return rc;
+  PackSuperP p;
+  p.fine = fine; p.coarse = coarse; p.init = init_coef; p.so = smokeout; p.idx = idx; p.resc = rescaler; p.out = state;
+  p.fine_sim = fine_sim_stride; p.coarse_sim = coarse_sim_stride; p.init_sim = init_sim_stride; p.so_sim = so_sim_stride;
+  p.F = F; p.nt = nt; p.nx = nx; p.nt_c = nt_c; p.nx_c = nx_c; p.pad_t = pad_t; p.pad_x = pad_x; p.C = C;
+  p.dW4 = make_fastdiv(pad_x >> 2); p.dPX = make_fastdiv(pad_x);
+  if (kind == WDNO_PACK_SUPER_TIME) pack_smoke_super_kernel<0><<<pk_grid(B, pad_t, C, pad_x), 256, 0, as_stream(s)>>>(p);
+  else pack_smoke_super_kernel<1><<<pk_grid(B, pad_t, C, pad_x), 256, 0, as_stream(s)>>>(p);
+  return wdno_check_launch();
+}
+
 // The same packing with the two condition channels computed from the PHYSICAL inputs inside the launch (the online pipeline fields -> state:
 // smoke/wave_trans_2d.py:150-170 + data_2d.py:156-221): rho0 [.][H0][W0] (the density at t = 0, e.g. a view into the fields tensor: its
 // per-simulation stride is given), curve [.][T0] (the smoke-out fraction per frame); zero-mode analysis with the wavelet's decomposition

@@ -9,8 +9,11 @@ HBM: the whole training set (smoke: 20 000 simulations x 3.35 MB of raw coeffici
   * ResidentSmokeLoader  : every simulation file is read ONCE (worker processes, pinned staging, in the order the first epoch needs them) into
                            resident stores of the RAW arrays, and every batch -- first epoch and after -- is packed on the GPU by
                            wdno_pack_smoke_state (csrc/pack.hip). From the second epoch on no host code touches the data.
+  * ResidentSuperSmokeLoader : the same for the list of level datasets of a super-resolution smoke model (SuperDataLoader's contract: one batch of
+                           one randomly chosen level per iteration): one set of stores per coefficient level, each file read once for all levels,
+                           every two-level batch packed by wdno_pack_smoke_super_state.
 
-Both iterate like `DataLoader(dataset, batch_size, shuffle=True, drop_last=False)` under a DistributedSampler (rank-disjoint shards of a padded
+The first two iterate like `DataLoader(dataset, batch_size, shuffle=True, drop_last=False)` under a DistributedSampler (rank-disjoint shards of a padded
 per-epoch permutation, reshuffled every epoch by `set_epoch`), yield DEVICE tensors, and are what the drop-in Trainers use when
 `Trainer.resident_data` is on and the data fits (TrainerCore.make_loader)."""
 import math
@@ -135,3 +138,116 @@ class ResidentSmokeLoader:
             state = pack_smoke_gpu(self.coef, self.init, self.so, self.rescaler, idx)
             shape = list(self.coef.shape[-3:])
             yield state, shape, None, torch.tensor(ids)
+
+
+class _RawLevelSims(Dataset):
+    def __init__(self, ds, ids, n_levels):
+        self.ds, self.ids, self.n_levels = ds, ids, n_levels
+
+    def __len__(self):
+        return len(self.ids)
+
+    def __getitem__(self, i):
+        return self.ds.raw_levels(self.ids[i], self.n_levels)
+
+
+class ResidentSuperSmokeLoader:
+    """`SuperDataLoader([Smoke_wave(..., is_super_model=True, N_downsample=i) for i < N], batch_size)` with the data resident in HBM: every
+    `__iter__` yields ONE batch of one randomly chosen level, `(state [B, pad_t, 82, pad_x, pad_x], shape, ori_shape, sim_id)` with `state` on the
+    device, pad_t / pad_x as Smoke_wave.__getitem__ sets them for the level (24 / 2^i and 40 for time, 24 and 40 / 2^i for space).
+
+    Stores: one set (coef, init, smokeout) per coefficient level 0 .. N; level i + 1 is dataset i's coarse level and dataset i + 1's fine level, so
+    nothing is held twice. A simulation's file is read ONCE, for all levels (Smoke_wave.raw_levels; the reference reads it per level's dataset and
+    per sample), by DataLoader workers with pinned hand-over, in the order the levels' current epochs will need the files; a batch whose
+    simulations are not all resident yet takes files from that stream until they are. Every batch is packed by one launch of
+    wdno_pack_smoke_super_state (csrc/pack.hip) with an index list.
+
+    Each level has its own _EpochOrder (seed `order_seed` + level, sharded by rank / world like a DistributedSampler), cursor and epoch counter;
+    the short last batch of a level's epoch is kept. `seed` (None: the global `random`) makes the level choice a private random.Random(seed), as
+    SuperDataLoader's does; ranks that are given the same `seed` draw the same level at every step and so walk each level's epochs in lockstep."""
+
+    def __init__(self, datasets, batch_size, device, shuffle=True, rank=0, world=1, seed=None, order_seed=0, num_workers=8, prefetch=4):
+        import random
+        datasets = list(datasets)
+        if not datasets or not all(getattr(d, 'is_super_model', False) and hasattr(d, 'raw_levels') for d in datasets):
+            raise ValueError('ResidentSuperSmokeLoader serves a list of super-resolution Smoke_wave datasets (the base dataset: ResidentSmokeLoader)')
+        if [d.N_downsample for d in datasets] != list(range(len(datasets))) or len({(d.path(0), len(d)) for d in datasets}) != 1:
+            raise ValueError('ResidentSuperSmokeLoader: the datasets must be the levels 0 .. N - 1 of one set of files')
+        self.ds, self.batch_size, self.device = datasets, batch_size, torch.device(device)
+        self.kind = 'space' if datasets[0].downsample_type == 'space' else 'time'
+        self.n_levels = len(datasets) + 1                          # coefficient levels held: dataset i pairs level i with level i + 1
+        self.samplers = [_EpochOrder(len(datasets[0]), rank, world, shuffle, order_seed + lvl) for lvl in range(len(datasets))]
+        self.epoch = [0] * len(datasets)
+        self._order = [None] * len(datasets)
+        self._cursor = [0] * len(datasets)
+        self._rng = random if seed is None else random.Random(seed)
+        self.num_workers, self.prefetch = num_workers, prefetch
+        self.rescaler = [d.RESCALER.reshape(-1).to(self.device, torch.float32) for d in datasets]
+        self.slot = {}                    # sim id -> row of the stores (the same row at every level)
+        self.coef = self.init = self.so = None
+        self._feeds, self._pending = [], set()
+
+    def pads(self, lvl):
+        return (24 // 2 ** lvl, 40) if self.kind == 'time' else (24, 40 // 2 ** lvl)
+
+    def resident_bytes(self):
+        return 0 if self.coef is None else 4 * sum(t.numel() for store in (self.coef, self.init, self.so) for t in store)
+
+    def __len__(self):
+        return len(self.ds) * math.ceil(len(self.samplers[0].indices()) / self.batch_size)
+
+    def _open_feed(self):
+        """Workers on every file the levels' current epochs still need and no stream has queued, batch by batch across the levels."""
+        rest = [o[c:] if o is not None else [] for o, c in zip(self._order, self._cursor)]
+        ids, seen = [], set(self.slot) | self._pending
+        for k in range(0, max(len(o) for o in rest), self.batch_size):
+            for o in rest:
+                for i in o[k:k + self.batch_size]:
+                    if i not in seen:
+                        seen.add(i)
+                        ids.append(i)
+        self._pending.update(ids)
+        dl = DataLoader(_RawLevelSims(self.ds[0], ids, self.n_levels), batch_size=None, shuffle=False, num_workers=self.num_workers,
+                        pin_memory=self.device.type == 'cuda',
+                        prefetch_factor=(max(2, self.prefetch * self.batch_size // max(1, self.num_workers)) if self.num_workers else None))
+        self._feeds.append(zip(ids, dl))
+
+    def _store(self, sim, levels):
+        if self.coef is None:
+            n = len(self.ds[0])
+            self.coef, self.init, self.so = ([torch.empty((n, *lv[k].shape), device=self.device, dtype=torch.float32) for lv in levels] for k in range(3))
+        s = len(self.slot)
+        for lvl, (coef, init, so) in enumerate(levels):
+            self.coef[lvl][s].copy_(coef, non_blocking=True)          # (pinned source: asynchronous copies on the launch stream, ahead of the pack)
+            self.init[lvl][s].copy_(init, non_blocking=True)
+            self.so[lvl][s].copy_(so, non_blocking=True)
+        self.slot[sim] = s
+        self._pending.discard(sim)
+
+    def _fetch(self, sim):
+        if sim not in self._pending:
+            self._open_feed()
+        while sim not in self.slot:
+            got = next(self._feeds[0], None)
+            if got is None:
+                self._feeds.pop(0)
+            else:
+                self._store(*got)
+
+    def __iter__(self):
+        from ddpm.data_2d import pack_smoke_super_batch
+        lvl = self._rng.randint(0, len(self.ds) - 1)
+        if self._order[lvl] is None or self._cursor[lvl] >= len(self._order[lvl]):
+            if self._order[lvl] is not None:
+                self.epoch[lvl] += 1
+            self.samplers[lvl].set_epoch(self.epoch[lvl])
+            self._order[lvl], self._cursor[lvl] = self.samplers[lvl].indices(), 0
+        ids = self._order[lvl][self._cursor[lvl]:self._cursor[lvl] + self.batch_size]
+        for i in ids:
+            if i not in self.slot:
+                self._fetch(i)
+        self._cursor[lvl] += len(ids)
+        idx = torch.tensor([self.slot[i] for i in ids], dtype=torch.int64).to(self.device, non_blocking=True)
+        pad_t, pad_x = self.pads(lvl)
+        state = pack_smoke_super_batch(self.coef[lvl], self.coef[lvl + 1], self.init[lvl], self.so[lvl], self.rescaler[lvl], self.kind, idx, pad_t, pad_x)
+        yield state, list(self.coef[lvl].shape[-3:]), None, torch.tensor(ids)

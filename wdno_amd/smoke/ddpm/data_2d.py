@@ -110,6 +110,75 @@ def pack_smoke_gpu(coef, init_coef, smokeout, rescaler, idx=None, pad_t=24, pad_
     return out
 
 
+def pack_smoke_super_batch(fine, coarse, init_coef, smokeout, rescaler, kind, idx=None, pad_t=24, pad_x=40):
+    """pack_smoke_state(..., coef_sub=...) for a whole batch of two-level simulations held on one device (the super-resolution models):
+    fine [N, F, 8, t, x, x] (level l), coarse [N, F, 8, t', x', x'] (level l + 1: t + 2 == 2 t' for kind 'time', x + 2 == 2 x' for 'space'),
+    init_coef [N, 4, x, x] or [N, 5, 4, x, x] (field 0 is used), smokeout [N, 2, t]; idx picks the simulations of the batch (None: all, in
+    order)  ->  states [B, pad_t, 16 F + 2, pad_x, pad_x] / rescaler. Index work only; equal to stacking pack_smoke_state per sample
+    (tests/test_host_super_loader.py). On CUDA tensors it is one launch of csrc/pack.hip (pack_smoke_super_gpu), bit-identical."""
+    if kind not in ('time', 'space'):
+        raise ValueError(f"kind must be 'time' or 'space', not {kind!r}")
+    if fine.is_cuda:
+        return pack_smoke_super_gpu(fine, coarse, init_coef, smokeout, rescaler, kind, idx, pad_t, pad_x)
+    if init_coef.dim() == 5:
+        init_coef = init_coef[:, 0]
+    if idx is not None:
+        idx = torch.as_tensor(idx, dtype=torch.int64)
+        fine, coarse, init_coef, smokeout = (t.index_select(0, idx) for t in (fine, coarse, init_coef, smokeout))
+    b, nf = fine.shape[0], fine.shape[1]
+    nt, nx = fine.shape[-3], fine.shape[-1]
+    w = fine.reshape(b, nf * 8, nt, nx, nx)
+    w_sub = coarse.reshape(b, nf * 8, *coarse.shape[-3:])
+    if kind == 'time':               # one replicated border frame on either side; the coarse frames twice each
+        w = w.index_select(2, (torch.arange(nt + 2) - 1).clamp(0, nt - 1))
+        w_sub = w_sub.repeat_interleave(2, dim=2)
+    else:                            # one replicated border row / column on every side; the coarse pixels as 2 x 2 patches
+        edge = (torch.arange(nx + 2) - 1).clamp(0, nx - 1)
+        w = w.index_select(3, edge).index_select(4, edge)
+        w_sub = w_sub.repeat_interleave(2, dim=3).repeat_interleave(2, dim=4)
+    assert w.shape == w_sub.shape, (w.shape, w_sub.shape)
+    both = torch.cat((w, w_sub), dim=1)
+    assert both.shape[-3] <= pad_t and both.shape[-1] <= pad_x and pad_t % 4 == 0 and pad_x % 2 == 0
+    data = F.pad(both, (0, pad_x - both.shape[-1], 0, pad_x - both.shape[-2], 0, pad_t - both.shape[-3]))
+    cond = init_coef.unsqueeze(2).expand(b, init_coef.shape[1], pad_t // 4, nx, nx).reshape(b, -1, nx, nx)
+    cond = F.pad(cond, (0, pad_x - nx, 0, pad_x - nx))
+    so = smokeout.permute(0, 2, 1)                                         # [B, t, 2]
+    so = so.reshape(b, 1, nt, 2, 1, 1).expand(b, 1, nt, 2, pad_x // 2, pad_x).reshape(b, 1, nt, pad_x, pad_x)
+    so = F.pad(so, (0, 0, 0, 0, 0, pad_t - nt))
+    state = torch.cat((data, cond.unsqueeze(1), so), dim=1)
+    return (state.permute(0, 2, 1, 3, 4) / torch.as_tensor(rescaler, dtype=torch.float32).reshape(1, -1, 1, 1)).contiguous()
+
+
+def pack_smoke_super_gpu(fine, coarse, init_coef, smokeout, rescaler, kind, idx=None, pad_t=24, pad_x=40):
+    """wdno_pack_smoke_super_state (csrc/pack.hip): two-level states [B, pad_t, 16 F + 2, pad_x, pad_x] / rescaler from device-resident coefficient
+    stores in one launch. fine [N, F, 8, nt, nx, nx] (level l), coarse [N, F, 8, nt_c, nx_c, nx_c] (level l + 1), init_coef [N, 4, nx, nx] or
+    [N, 5, 4, nx, nx] and smokeout [N, 2, nt] of level l, as the offline transform stores them; kind 'time' / 'space'; idx (int64 [B]) picks the
+    simulations of the batch from the N resident ones (None: all of them, in order). The shape rules are the library's (include/wdno_hip.h)."""
+    from wdno_amd import _lib
+    from wdno_amd.ops import _lib_, _p, _stream
+    if kind not in ('time', 'space'):
+        raise ValueError(f"kind must be 'time' or 'space', not {kind!r}")
+    for t, name in ((fine, 'fine'), (coarse, 'coarse'), (init_coef, 'init_coef'), (smokeout, 'smokeout')):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError(f'wdno_amd pack_smoke_super_gpu: {name} must be a contiguous float32 tensor on the GPU')
+    n, nf = fine.shape[0], fine.shape[1]
+    nt, nx = fine.shape[-3], fine.shape[-1]
+    nt_c, nx_c = coarse.shape[-3], coarse.shape[-1]
+    assert tuple(fine.shape[2:]) == (8, nt, nx, nx) and tuple(coarse.shape) == (n, nf, 8, nt_c, nx_c, nx_c)
+    assert tuple(init_coef.shape[-3:]) == (4, nx, nx) and tuple(smokeout.shape[1:]) == (2, nt) and init_coef.shape[0] == smokeout.shape[0] == n
+    c = 16 * nf + 2
+    r = torch.as_tensor(rescaler, dtype=torch.float32).reshape(-1).to(fine.device)
+    assert r.numel() == c, f'rescaler has {r.numel()} entries, the state {c} channels'
+    if idx is not None:
+        idx = idx.to(device=fine.device, dtype=torch.int64).contiguous()
+    b = n if idx is None else idx.numel()
+    out = torch.empty((b, pad_t, c, pad_x, pad_x), device=fine.device, dtype=torch.float32)
+    _lib.check(_lib_().wdno_pack_smoke_super_state(_p(fine), fine[0].numel(), _p(coarse), coarse[0].numel(), _p(init_coef), init_coef[0].numel(),
+                                                   _p(smokeout), smokeout[0].numel(), _p(idx), _p(r), _p(out), b, nf, nt, nx, nt_c, nx_c,
+                                                   1 if kind == 'space' else 0, pad_t, pad_x, _stream()), 'pack_smoke_super_state')
+    return out
+
+
 def pack_smoke_fields(fields, curve, rescaler, wave='bior1.3', pad_t=24, pad_x=40, direct=True):
     """fields [B, F, T, H, W] (field 0 = density) and the smoke-out curve [B, T], resident in HBM -> states [B, pad_t, 8 F + 2, pad_x, pad_x] /
     rescaler in TWO launches: the fused 3-D analysis of all fields whose store lands in the state (sub-band -> channel, frame -> frame, already
@@ -184,6 +253,13 @@ class Smoke_wave(Dataset):
         lvl = self.N_downsample
         return (db['coef'][lvl].to(torch.float32).contiguous(), db['init_coef'][lvl][0].to(torch.float32).contiguous(),
                 db['smokeout'][lvl].to(torch.float32).contiguous())
+
+    def raw_levels(self, sim_id, n_levels):
+        """`raw` for the levels 0 .. n_levels - 1 of simulation sim_id from ONE read of its file: a list of (coef, init_coef of the density,
+        smokeout) -- what wdno_amd.loader.ResidentSuperSmokeLoader keeps in HBM for the super-resolution models (level l + 1 is level l's coarse)."""
+        db = torch.load(self.path(sim_id), weights_only=False)
+        return [(db['coef'][lvl].to(torch.float32).contiguous(), db['init_coef'][lvl][0].to(torch.float32).contiguous(),
+                 db['smokeout'][lvl].to(torch.float32).contiguous()) for lvl in range(n_levels)]
 
     def __getitem__(self, sim_id):
         db = torch.load(self.path(sim_id), weights_only=False)

@@ -456,9 +456,12 @@ class Trainer(_TrainerCore):
             self.ds = dataset
         if isinstance(self.ds, (list, tuple)):
             from ddpm.data_2d import SuperDataLoader
-            workers = 4 if self.num_workers is None else self.num_workers
-            dl = SuperDataLoader(self.ds, batch_size=self.local_batch_size, shuffle=True, pin_memory=True, num_workers=workers,
-                                 seed=self.data_seed if self.world > 1 else None)
+            # every level's coefficient files in HBM, two-level batches packed on the GPU (wdno_amd.loader.ResidentSuperSmokeLoader) where they fit
+            dl = self.make_super_loader(self.ds, self.local_batch_size, 16 if self.num_workers is None else self.num_workers)
+            if dl is None:
+                workers = 4 if self.num_workers is None else self.num_workers
+                dl = SuperDataLoader(self.ds, batch_size=self.local_batch_size, shuffle=True, pin_memory=True, num_workers=workers,
+                                     seed=self.data_seed if self.world > 1 else None)
         else:
             workers = 16 if self.num_workers is None else self.num_workers
             dl = self.make_loader(self.ds, self.local_batch_size, workers)

@@ -846,8 +846,27 @@ class TrainerCore:
         return DataLoader(dataset, batch_size=batch_size, shuffle=shuffle and sampler is None, sampler=sampler, pin_memory=True,
                           num_workers=num_workers, drop_last=False)
 
+    def make_super_loader(self, datasets, batch_size, num_workers):
+        """The resident pipeline for the list of level datasets of a super-resolution smoke model (wdno_amd.loader.ResidentSuperSmokeLoader), or
+        None where the reference's SuperDataLoader has to serve: resident_data off, datasets without `raw_levels`, no first file to size the
+        levels from, or a training set that would take half of the free HBM or more (make_loader's rule, over all levels)."""
+        if not (self.resident_data and len(datasets) and all(hasattr(d, 'raw_levels') and getattr(d, 'is_super_model', False) for d in datasets)):
+            return None
+        from . import loader as L
+        try:
+            levels = datasets[0].raw_levels(0, len(datasets) + 1)
+        except OSError:
+            return None
+        sim_bytes = 4 * sum(t.numel() for lv in levels for t in lv)
+        if len(datasets[0]) * sim_bytes >= torch.cuda.mem_get_info(self._device)[0] // 2:
+            return None
+        # ranks agree on the per-level permutations (the shards of an epoch are disjoint) and, by a common level seed, on the level of every step
+        order_seed = 0 if self.world > 1 else int(torch.empty((), dtype=torch.int64).random_().item())
+        return L.ResidentSuperSmokeLoader(datasets, batch_size, self._device, True, self.rank, self.world, seed=1234 if self.world > 1 else None,
+                                          order_seed=order_seed, num_workers=num_workers)
+
     # ------------------------------------------------------------------ one optimisation step (T1 / T2)
-    use_graph = True            # the step (loss -> backward -> gradient gather) is replayed from one captured HIP graph per batch shape
+    use_graph = True           # the step (loss -> backward -> gradient gather) is replayed from one captured HIP graph per batch shape
                                 # (CapturedStep; gradient_accumulate_every == 1 only; the first step of a shape runs launch by launch, the capture
                                 # follows it). A class attribute like num_workers: the constructors keep the reference's parameter lists.
                                 # Bit-identical to the launch-by-launch step (tests/test_gpu_trainer.py); False: every step launch by launch.
