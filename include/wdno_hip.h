@@ -669,6 +669,27 @@ int wdno_ddim_update(const float* x, const float* eps, const float* noise, const
 int wdno_ddim_update_dev(const float* x, const float* eps, const float* noise, const int64_t* t,
                          const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* coef_dev,
                          float* x_next, float* x_start, int64_t B, int64_t per_sample, wdno_stream_t s);
+/* What the launches above do (nothing is launched, no device is needed; the entry points ask the same code). Every operation has two forms:
+ * WDNO_FORM_SCALAR, one element per work item with 64-bit index arithmetic on a grid of grid_x blocks (grid_y = 1), and WDNO_FORM_FLOAT4,
+ * four elements per work item with 32-bit index arithmetic, for the loss and the updates with the sample on the grid's y axis (grid_y = B).
+ * Blocks have 256 threads and walk the work items with a stride of grid_x * 256. align_mask: the addresses of the tensor operands the entry
+ * point is given (not the tables, t or the scalars), OR-ed together; only the low four bits matter, a NULL operand adds nothing.
+ *   wdno_cond_plan        : wdno_q_sample_cond (x0 | noise | x_out | target_out) and wdno_apply_cond (x | src). float4 needs W % 4 == 0,
+ *                           fewer than 2^31 elements and 16-byte alignment.
+ *   wdno_weighted_mse_plan: backward == 0 wdno_weighted_mse, else wdno_weighted_mse_bwd (out | target | grad). float4 needs inner % 4 == 0,
+ *                           B <= 2048, 16-byte alignment and, forward, at least B doubles of workspace partials (stream grid of B * per_sample
+ *                           not below B); the forward launch is followed by one block that adds the grid_x * grid_y partial sums. ws_bytes
+ *                           is read by the forward only.
+ *   wdno_update_plan      : wdno_p_sample_update, wdno_ddim_update, wdno_ddim_update_dev (x | eps | noise | x_next | x_start). float4 needs
+ *                           per_sample % 4 == 0, B <= 65535 and 16-byte alignment.
+ * rc = the code the launch would return for these arguments, short of WDNO_ELAUNCH and of the NULL checks of pointers the query does not see
+ * (WDNO_EINVAL, WDNO_EWORKSPACE); the other fields are 0 then. The functions return WDNO_EINVAL only for out == NULL. */
+enum { WDNO_FORM_SCALAR = 0, WDNO_FORM_FLOAT4 = 1 };
+typedef struct { int form, grid_x, grid_y, rc; } wdno_diffusion_plan;
+int wdno_cond_plan(const wdno_cond_desc* c, unsigned align_mask, wdno_diffusion_plan* out);
+int wdno_weighted_mse_plan(int64_t B, int64_t per_sample, int C, int64_t inner, size_t ws_bytes, unsigned align_mask, int backward,
+                           wdno_diffusion_plan* out);
+int wdno_update_plan(int64_t B, int64_t per_sample, unsigned align_mask, wdno_diffusion_plan* out);
 
 /* ------------------------------------------------------------------------------------------------ trainer step
  * Flat-buffer optimiser (train_diffusion.py:117,211-216 ; diffusion_2d.py:1159,1283-1291).

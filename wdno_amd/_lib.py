@@ -62,7 +62,14 @@ class LayerNormPlan(C.Structure):            # include/wdno_hip.h: wdno_ln_plan
     _fields_ = [(k, I) for k in ('tpr', 'vpl', 'rows_per_block', 'blocks', 'max_rows_walk', 'rc')]
 
 
-class DwtPlan(C.Structure):                  # include/wdno_hip.h: wdno_dwt_plan
+class DiffusionPlan(C.Structure):            # include/wdno_hip.h: wdno_diffusion_plan
+    _fields_ = [(k, I) for k in ('form', 'grid_x', 'grid_y', 'rc')]
+
+
+DIFFUSION_FORMS = ('scalar', 'float4')                                                                       # WDNO_FORM_*
+
+
+class DwtPlan(C.Structure):                 # include/wdno_hip.h: wdno_dwt_plan
     _fields_ = [(k, I) for k in ('family', 'variant', 'nh', 'tiles_h', 'tiles_t', 'blocks', 'lds_bytes', 'rc')]
 
 
@@ -277,6 +284,9 @@ PROTOTYPES = {
     'wdno_p_sample_update': (I, [P, P, P, P, P, P, P, P, P, P, P, L, L, I, P]),
     'wdno_ddim_update': (I, [P, P, P, P, P, P, F, F, F, P, P, L, L, P]),
     'wdno_ddim_update_dev': (I, [P, P, P, P, P, P, P, P, P, L, L, P]),
+    'wdno_cond_plan': (I, [PC, C.c_uint, P]),
+    'wdno_weighted_mse_plan': (I, [L, L, I, L, Z, C.c_uint, I, P]),
+    'wdno_update_plan': (I, [L, L, C.c_uint, P]),
     'wdno_sumsq_ws_bytes': (Z, [L]),
     'wdno_sumsq': (I, [P, L, P, P, Z, P]),
     'wdno_adam_clip_step': (I, [P, P, P, P, L, P, F, F, F, F, F, F, I, P]),

@@ -103,26 +103,46 @@ __global__ __launch_bounds__(256) void apply_cond4_kernel(float4* __restrict__ x
     x[i] = make_float4(o[0], o[1], o[2], o[3]);
   }
 }
-static inline bool vec4_ok(const wdno_cond_desc* c, int64_t total, const void* a, const void* b, const void* e, const void* f) {
-  return (c->W & 3) == 0 && total < (1ll << 31) && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)e) | ((uintptr_t)f)) & 15) == 0;
-}
 static int check_cond(const wdno_cond_desc* c) {
   if (!c || (c->tree != 0 && c->tree != 1)) return WDNO_EINVAL;
   if (c->B <= 0 || c->F <= 0 || c->C <= 0 || c->H <= 0 || c->W <= 0) return WDNO_EINVAL;
   if (c->tree == 1 && c->F != 1) return WDNO_EINVAL;
   return WDNO_OK;
 }
+// The one place that chooses the form and the grid of the two condition launches (wdno_cond_plan asks it too): float4 when W % 4 == 0, the
+// tensor has fewer than 2^31 elements and every pointer is 16-byte aligned (`align` = the pointers OR-ed together), scalar otherwise.
+static inline bool vec4_ok(const wdno_cond_desc* c, int64_t total, uintptr_t align) {
+  return (c->W & 3) == 0 && total < (1ll << 31) && (align & 15) == 0;
+}
+static inline uintptr_t ptr_bits(const void* p) { return (uintptr_t)p; }
+static int cond_decide(const wdno_cond_desc* c, uintptr_t align, wdno_diffusion_plan* p, int64_t* total_out) {
+  *p = wdno_diffusion_plan{0, 0, 0, check_cond(c)};
+  if (p->rc) return p->rc;
+  const int64_t total = (int64_t)c->B * c->F * c->C * c->H * c->W;
+  p->form = vec4_ok(c, total, align) ? WDNO_FORM_FLOAT4 : WDNO_FORM_SCALAR;
+  p->grid_x = stream_grid(p->form == WDNO_FORM_FLOAT4 ? total / 4 : total, 256);
+  p->grid_y = 1;
+  *total_out = total;
+  return WDNO_OK;
+}
+extern "C" int wdno_cond_plan(const wdno_cond_desc* c, unsigned align_mask, wdno_diffusion_plan* out) {
+  if (!out) return WDNO_EINVAL;
+  int64_t total;
+  cond_decide(c, align_mask, out, &total);
+  return WDNO_OK;
+}
 extern "C" int wdno_q_sample_cond(const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
                                   float* x_out, float* target_out, const wdno_cond_desc* c, wdno_stream_t s) {
-  int rc = check_cond(c);
+  wdno_diffusion_plan p;
+  int64_t total;
+  int rc = cond_decide(c, ptr_bits(x0) | ptr_bits(noise) | ptr_bits(x_out) | ptr_bits(target_out), &p, &total);
   if (rc) return rc;
-  int64_t total = (int64_t)c->B * c->F * c->C * c->H * c->W;
-  if (vec4_ok(c, total, x0, noise, x_out, target_out)) {
-    q_sample_cond4_kernel<<<stream_grid(total / 4, 256), 256, 0, as_stream(s)>>>((const float4*)x0, (const float4*)noise, t, sqrt_ac, sqrt_1mac,
-                                                                             (float4*)x_out, (float4*)target_out, *c, (unsigned)(total / 4));
+  if (p.form == WDNO_FORM_FLOAT4) {
+    q_sample_cond4_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>((const float4*)x0, (const float4*)noise, t, sqrt_ac, sqrt_1mac,
+                                                              (float4*)x_out, (float4*)target_out, *c, (unsigned)(total / 4));
     return wdno_check_launch();
   }
-  q_sample_cond_kernel<<<stream_grid(total, 256), 256, 0, as_stream(s)>>>(x0, noise, t, sqrt_ac, sqrt_1mac, x_out, target_out, *c, total);
+  q_sample_cond_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>(x0, noise, t, sqrt_ac, sqrt_1mac, x_out, target_out, *c, total);
   return wdno_check_launch();
 }
 
@@ -137,14 +157,15 @@ __global__ __launch_bounds__(256) void apply_cond_kernel(float* __restrict__ x, 
   }
 }
 extern "C" int wdno_apply_cond(float* x, const float* src, const wdno_cond_desc* c, wdno_stream_t s) {
-  int rc = check_cond(c);
+  wdno_diffusion_plan p;
+  int64_t total;
+  int rc = cond_decide(c, ptr_bits(x) | ptr_bits(src), &p, &total);
   if (rc) return rc;
-  int64_t total = (int64_t)c->B * c->F * c->C * c->H * c->W;
-  if (vec4_ok(c, total, x, src, nullptr, nullptr)) {
-    apply_cond4_kernel<<<stream_grid(total / 4, 256), 256, 0, as_stream(s)>>>((float4*)x, (const float4*)src, *c, (unsigned)(total / 4));
+  if (p.form == WDNO_FORM_FLOAT4) {
+    apply_cond4_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>((float4*)x, (const float4*)src, *c, (unsigned)(total / 4));
     return wdno_check_launch();
   }
-  apply_cond_kernel<<<stream_grid(total, 256), 256, 0, as_stream(s)>>>(x, src, *c, total);
+  apply_cond_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>(x, src, *c, total);
   return wdno_check_launch();
 }
 
@@ -210,27 +231,51 @@ __global__ __launch_bounds__(256) void wmse4_kernel(const float4* __restrict__ o
     if (threadIdx.x == 0) ws[blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
   }
 }
-static inline bool wmse4_ok(int64_t B, int64_t per_sample, int64_t inner, const void* a, const void* b, const void* c) {
-  return (inner & 3) == 0 && (per_sample & 3) == 0 && per_sample / 4 < (1ll << 31) && B <= 2048 &&
-         ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
+static inline bool wmse4_ok(int64_t B, int64_t per_sample, int64_t inner, uintptr_t align) {
+  return (inner & 3) == 0 && (per_sample & 3) == 0 && per_sample / 4 < (1ll << 31) && B <= 2048 && (align & 15) == 0;
 }
 extern "C" size_t wdno_weighted_mse_ws_bytes(int64_t n) { return (size_t)stream_grid(n, 256) * sizeof(double); }
+// The one place that chooses the form and the grid of the loss launches (wdno_weighted_mse_plan asks it too). `align` = out | target | grad.
+// Forward: the float4 form leaves grid_x * B partial sums, which must fit the nb = stream_grid(total) doubles of the workspace -- nb < B
+// (fewer than about 256 elements per sample, or B > 2048) goes to the scalar form. Backward: ~2048 blocks in all.
+static int wmse_decide(bool bwd, int64_t B, int64_t per_sample, int C, int64_t inner, size_t ws_bytes, uintptr_t align, wdno_diffusion_plan* p) {
+  *p = wdno_diffusion_plan{0, 0, 0, WDNO_OK};
+  if (!(B > 0 && per_sample > 0 && C > 0 && inner > 0)) return p->rc = WDNO_EINVAL;
+  const int64_t total = B * per_sample;
+  if (!bwd && ws_bytes < wdno_weighted_mse_ws_bytes(total)) return p->rc = WDNO_EWORKSPACE;
+  const int nb = stream_grid(total, 256);
+  if (wmse4_ok(B, per_sample, inner, align) && (bwd || nb >= B)) {
+    p->form = WDNO_FORM_FLOAT4;
+    p->grid_x = (int)std::min<int64_t>(cdiv64(per_sample / 4, 256), bwd ? std::max<int64_t>(1, 2048 / B) : nb / B);
+    p->grid_y = (int)B;
+  } else {
+    p->form = WDNO_FORM_SCALAR;
+    p->grid_x = nb;
+    p->grid_y = 1;
+  }
+  return WDNO_OK;
+}
+extern "C" int wdno_weighted_mse_plan(int64_t B, int64_t per_sample, int C, int64_t inner, size_t ws_bytes, unsigned align_mask, int backward,
+                                      wdno_diffusion_plan* out) {
+  if (!out) return WDNO_EINVAL;
+  wmse_decide(backward != 0, B, per_sample, C, inner, ws_bytes, align_mask, out);
+  return WDNO_OK;
+}
 extern "C" int wdno_weighted_mse(const float* out, const float* target, const float* wc, const float* wb, float inv_count,
                                  float* loss, float* grad, int64_t B, int64_t per_sample, int C, int64_t inner,
                                  void* ws, size_t ws_bytes, wdno_stream_t s) {
-  WDNO_REQUIRE(B > 0 && per_sample > 0 && C > 0 && inner > 0);
-  int64_t total = B * per_sample;
-  if (ws_bytes < wdno_weighted_mse_ws_bytes(total)) return WDNO_EWORKSPACE;
-  int nb = stream_grid(total, 256);
-  if (wmse4_ok(B, per_sample, inner, out, target, grad) && nb >= B) {
-    const int gx = (int)std::min<int64_t>(cdiv64(per_sample / 4, 256), nb / B);         // gx * B partial sums <= the workspace's nb
-    wmse4_kernel<false><<<dim3((unsigned)gx, (unsigned)B), 256, 0, as_stream(s)>>>((const float4*)out, (const float4*)target, wc, wb, inv_count, nullptr,
-                                                                                 (float4*)grad, (double*)ws, (unsigned)(per_sample / 4), C, (unsigned)(inner / 4));
-    wmse_final_kernel<<<1, 256, 0, as_stream(s)>>>((const double*)ws, gx * (int)B, loss, inv_count);
+  wdno_diffusion_plan p;
+  int rc = wmse_decide(false, B, per_sample, C, inner, ws_bytes, ptr_bits(out) | ptr_bits(target) | ptr_bits(grad), &p);
+  if (rc) return rc;
+  if (p.form == WDNO_FORM_FLOAT4) {
+    wmse4_kernel<false><<<dim3((unsigned)p.grid_x, (unsigned)p.grid_y), 256, 0, as_stream(s)>>>((const float4*)out, (const float4*)target, wc, wb, inv_count,
+                                                                                              nullptr, (float4*)grad, (double*)ws, (unsigned)(per_sample / 4), C,
+                                                                                              (unsigned)(inner / 4));
+    wmse_final_kernel<<<1, 256, 0, as_stream(s)>>>((const double*)ws, p.grid_x * p.grid_y, loss, inv_count);
     return wdno_check_launch();
   }
-  wmse_kernel<<<nb, 256, 0, as_stream(s)>>>(out, target, wc, wb, inv_count, grad, (double*)ws, total, per_sample, C, inner);
-  wmse_final_kernel<<<1, 256, 0, as_stream(s)>>>((const double*)ws, nb, loss, inv_count);
+  wmse_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>(out, target, wc, wb, inv_count, grad, (double*)ws, B * per_sample, per_sample, C, inner);
+  wmse_final_kernel<<<1, 256, 0, as_stream(s)>>>((const double*)ws, p.grid_x, loss, inv_count);
   return wdno_check_launch();
 }
 
@@ -250,15 +295,17 @@ __global__ __launch_bounds__(256) void wmse_bwd_kernel(const float* __restrict__
 extern "C" int wdno_weighted_mse_bwd(const float* out, const float* target, const float* wc, const float* wb, float inv_count,
                                      const float* gscale, float* grad, int64_t B, int64_t per_sample, int C, int64_t inner,
                                      wdno_stream_t s) {
-  WDNO_REQUIRE(B > 0 && per_sample > 0 && C > 0 && inner > 0 && grad != nullptr);
-  int64_t total = B * per_sample;
-  if (wmse4_ok(B, per_sample, inner, out, target, grad)) {
-    const int gx = (int)std::min<int64_t>(cdiv64(per_sample / 4, 256), std::max<int64_t>(1, 2048 / B));
-    wmse4_kernel<true><<<dim3((unsigned)gx, (unsigned)B), 256, 0, as_stream(s)>>>((const float4*)out, (const float4*)target, wc, wb, inv_count, gscale,
-                                                                                (float4*)grad, nullptr, (unsigned)(per_sample / 4), C, (unsigned)(inner / 4));
+  WDNO_REQUIRE(grad != nullptr);
+  wdno_diffusion_plan p;
+  int rc = wmse_decide(true, B, per_sample, C, inner, 0, ptr_bits(out) | ptr_bits(target) | ptr_bits(grad), &p);
+  if (rc) return rc;
+  if (p.form == WDNO_FORM_FLOAT4) {
+    wmse4_kernel<true><<<dim3((unsigned)p.grid_x, (unsigned)p.grid_y), 256, 0, as_stream(s)>>>((const float4*)out, (const float4*)target, wc, wb, inv_count,
+                                                                                             gscale, (float4*)grad, nullptr, (unsigned)(per_sample / 4), C,
+                                                                                             (unsigned)(inner / 4));
     return wdno_check_launch();
   }
-  wmse_bwd_kernel<<<stream_grid(total, 256), 256, 0, as_stream(s)>>>(out, target, wc, wb, inv_count, gscale, grad, total, per_sample, C, inner);
+  wmse_bwd_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>(out, target, wc, wb, inv_count, gscale, grad, B * per_sample, per_sample, C, inner);
   return wdno_check_launch();
 }
 
@@ -337,9 +384,8 @@ __global__ __launch_bounds__(256) void ddim4_kernel(const float4* __restrict__ x
     if (xs) xs[base + i] = make_float4(st4[0], st4[1], st4[2], st4[3]);
   }
 }
-static inline bool upd4_ok(int64_t B, int64_t per_sample, const void* a, const void* b, const void* c, const void* d, const void* e) {
-  return (per_sample & 3) == 0 && per_sample / 4 < (1ll << 31) && B <= 65535 &&
-         ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e)) & 15) == 0;
+static inline bool upd4_ok(int64_t B, int64_t per_sample, uintptr_t align) {
+  return (per_sample & 3) == 0 && per_sample / 4 < (1ll << 31) && B <= 65535 && (align & 15) == 0;
 }
 static inline dim3 upd4_grid(int64_t B, int64_t per4) {
   int64_t gx = cdiv64(per4, 256);
@@ -347,20 +393,46 @@ static inline dim3 upd4_grid(int64_t B, int64_t per4) {
   if (gx > cap) gx = cap;
   return dim3((unsigned)gx, (unsigned)B);
 }
+// The one place that chooses the form and the grid of the three sampler updates (wdno_update_plan asks it too).
+// `align` = x | eps | noise | x_next | x_start (a NULL noise or x_start adds nothing).
+static int upd_decide(int64_t B, int64_t per_sample, uintptr_t align, wdno_diffusion_plan* p) {
+  *p = wdno_diffusion_plan{0, 0, 0, WDNO_OK};
+  if (!(B > 0 && per_sample > 0)) return p->rc = WDNO_EINVAL;
+  if (upd4_ok(B, per_sample, align)) {
+    const dim3 g = upd4_grid(B, per_sample / 4);
+    p->form = WDNO_FORM_FLOAT4;
+    p->grid_x = (int)g.x;
+    p->grid_y = (int)g.y;
+  } else {
+    p->form = WDNO_FORM_SCALAR;
+    p->grid_x = stream_grid(B * per_sample, 256);
+    p->grid_y = 1;
+  }
+  return WDNO_OK;
+}
+static inline uintptr_t upd_align(const void* a, const void* b, const void* c, const void* d, const void* e) {
+  return ptr_bits(a) | ptr_bits(b) | ptr_bits(c) | ptr_bits(d) | ptr_bits(e);
+}
+extern "C" int wdno_update_plan(int64_t B, int64_t per_sample, unsigned align_mask, wdno_diffusion_plan* out) {
+  if (!out) return WDNO_EINVAL;
+  upd_decide(B, per_sample, align_mask, out);
+  return WDNO_OK;
+}
 extern "C" int wdno_p_sample_update(const float* x, const float* eps, const float* noise, const int64_t* t,
                                     const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* pm1, const float* pm2,
                                     const float* plogvar, float* x_next, float* x_start, int64_t B, int64_t per_sample, int clamp,
                                     wdno_stream_t s) {
-  WDNO_REQUIRE(B > 0 && per_sample > 0);
-  int64_t total = B * per_sample;
-  if (upd4_ok(B, per_sample, x, eps, noise, x_next, x_start)) {
-    p_sample4_kernel<<<upd4_grid(B, per_sample / 4), 256, 0, as_stream(s)>>>((const float4*)x, (const float4*)eps, (const float4*)noise, t, sqrt_recip_ac,
+  wdno_diffusion_plan p;
+  int rc = upd_decide(B, per_sample, upd_align(x, eps, noise, x_next, x_start), &p);
+  if (rc) return rc;
+  if (p.form == WDNO_FORM_FLOAT4) {
+    p_sample4_kernel<<<dim3((unsigned)p.grid_x, (unsigned)p.grid_y), 256, 0, as_stream(s)>>>((const float4*)x, (const float4*)eps, (const float4*)noise, t, sqrt_recip_ac,
                                                                            sqrt_recipm1_ac, pm1, pm2, plogvar, (float4*)x_next, (float4*)x_start,
                                                                            (unsigned)(per_sample / 4), clamp);
     return wdno_check_launch();
   }
-  p_sample_kernel<<<stream_grid(total, 256), 256, 0, as_stream(s)>>>(x, eps, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, pm1, pm2, plogvar,
-                                                                   x_next, x_start, total, per_sample, clamp);
+  p_sample_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>(x, eps, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, pm1, pm2, plogvar,
+                                                      x_next, x_start, B * per_sample, per_sample, clamp);
   return wdno_check_launch();
 }
 
@@ -389,30 +461,33 @@ __global__ __launch_bounds__(256) void ddim_kernel(const float* __restrict__ x, 
 extern "C" int wdno_ddim_update(const float* x, const float* eps, const float* noise, const int64_t* t,
                                 const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, float sqrt_an, float c, float sigma,
                                 float* x_next, float* x_start, int64_t B, int64_t per_sample, wdno_stream_t s) {
-  WDNO_REQUIRE(B > 0 && per_sample > 0);
-  int64_t total = B * per_sample;
-  if (upd4_ok(B, per_sample, x, eps, noise, x_next, x_start)) {
-    ddim4_kernel<<<upd4_grid(B, per_sample / 4), 256, 0, as_stream(s)>>>((const float4*)x, (const float4*)eps, (const float4*)noise, t, sqrt_recip_ac,
+  wdno_diffusion_plan p;
+  int rc = upd_decide(B, per_sample, upd_align(x, eps, noise, x_next, x_start), &p);
+  if (rc) return rc;
+  if (p.form == WDNO_FORM_FLOAT4) {
+    ddim4_kernel<<<dim3((unsigned)p.grid_x, (unsigned)p.grid_y), 256, 0, as_stream(s)>>>((const float4*)x, (const float4*)eps, (const float4*)noise, t, sqrt_recip_ac,
                                                                        sqrt_recipm1_ac, sqrt_an, c, sigma, nullptr, (float4*)x_next, (float4*)x_start,
                                                                        (unsigned)(per_sample / 4));
     return wdno_check_launch();
   }
-  ddim_kernel<<<stream_grid(total, 256), 256, 0, as_stream(s)>>>(x, eps, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_an, c, sigma,
-                                                               nullptr, x_next, x_start, total, per_sample);
+  ddim_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>(x, eps, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_an, c, sigma,
+                                                  nullptr, x_next, x_start, B * per_sample, per_sample);
   return wdno_check_launch();
 }
 extern "C" int wdno_ddim_update_dev(const float* x, const float* eps, const float* noise, const int64_t* t,
                                     const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* coef_dev,
                                     float* x_next, float* x_start, int64_t B, int64_t per_sample, wdno_stream_t s) {
-  WDNO_REQUIRE(B > 0 && per_sample > 0 && coef_dev != nullptr && noise != nullptr);
-  int64_t total = B * per_sample;
-  if (upd4_ok(B, per_sample, x, eps, noise, x_next, x_start)) {
-    ddim4_kernel<<<upd4_grid(B, per_sample / 4), 256, 0, as_stream(s)>>>((const float4*)x, (const float4*)eps, (const float4*)noise, t, sqrt_recip_ac,
+  WDNO_REQUIRE(coef_dev != nullptr && noise != nullptr);
+  wdno_diffusion_plan p;
+  int rc = upd_decide(B, per_sample, upd_align(x, eps, noise, x_next, x_start), &p);
+  if (rc) return rc;
+  if (p.form == WDNO_FORM_FLOAT4) {
+    ddim4_kernel<<<dim3((unsigned)p.grid_x, (unsigned)p.grid_y), 256, 0, as_stream(s)>>>((const float4*)x, (const float4*)eps, (const float4*)noise, t, sqrt_recip_ac,
                                                                        sqrt_recipm1_ac, 0.f, 0.f, 0.f, coef_dev, (float4*)x_next, (float4*)x_start,
                                                                        (unsigned)(per_sample / 4));
     return wdno_check_launch();
   }
-  ddim_kernel<<<stream_grid(total, 256), 256, 0, as_stream(s)>>>(x, eps, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, 0.f, 0.f, 0.f,
-                                                               coef_dev, x_next, x_start, total, per_sample);
+  ddim_kernel<<<p.grid_x, 256, 0, as_stream(s)>>>(x, eps, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, 0.f, 0.f, 0.f,
+                                                  coef_dev, x_next, x_start, B * per_sample, per_sample);
   return wdno_check_launch();
 }

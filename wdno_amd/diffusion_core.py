@@ -190,6 +190,37 @@ def ddim_update_dev(mod, x, eps, noise, t, coef_dev):
     return x_next, x_start
 
 
+def _plan(pl):
+    """dict(form 'scalar' | 'float4' (None when rc != 0), grid_x, grid_y, rc) of a wdno_diffusion_plan"""
+    return dict(form=_lib.DIFFUSION_FORMS[pl.form] if pl.rc == 0 else None, grid_x=pl.grid_x, grid_y=pl.grid_y, rc=pl.rc)
+
+
+def cond_plan(desc, align_mask=0):
+    """What q_sample_cond / apply_cond launch under `desc` for operands whose addresses OR to `align_mask` (csrc/diffusion.hip: cond_decide).
+    No launch, no device needed."""
+    pl = _lib.DiffusionPlan()
+    _lib.check(_lib_().wdno_cond_plan(C.byref(desc), int(align_mask) & 0xffffffff, C.byref(pl)), 'cond_plan')
+    return _plan(pl)
+
+
+def weighted_mse_plan(b, per_sample, n_chan, inner, backward=False, ws_bytes=None, align_mask=0):
+    """What weighted_mse (forward, or its backward) launches (csrc/diffusion.hip: wmse_decide). ws_bytes None: the workspace the forward asks
+    for. No launch, no device needed."""
+    pl = _lib.DiffusionPlan()
+    if ws_bytes is None:
+        ws_bytes = _lib_().wdno_weighted_mse_ws_bytes(int(b) * int(per_sample))
+    _lib.check(_lib_().wdno_weighted_mse_plan(int(b), int(per_sample), int(n_chan), int(inner), int(ws_bytes), int(align_mask) & 0xffffffff,
+                                              int(bool(backward)), C.byref(pl)), 'weighted_mse_plan')
+    return _plan(pl)
+
+
+def update_plan(b, per_sample, align_mask=0):
+    """What p_sample_update / ddim_update / ddim_update_dev launch (csrc/diffusion.hip: upd_decide). No launch, no device needed."""
+    pl = _lib.DiffusionPlan()
+    _lib.check(_lib_().wdno_update_plan(int(b), int(per_sample), int(align_mask) & 0xffffffff, C.byref(pl)), 'update_plan')
+    return _plan(pl)
+
+
 def ac_host(mod):
     """Host copy of the module's CURRENT `alphas_cumprod` buffer (the scalar DDIM coefficients are evaluated on the host with the
     reference's fp32 tensor arithmetic). Re-read whenever the buffer changed: `load_state_dict` of an upstream checkpoint replaces the
