@@ -138,6 +138,34 @@ int wdno_pack_smoke_super_state(const float* fine, int64_t fine_sim_stride, cons
                                 const float* init_coef, int64_t init_sim_stride, const float* smokeout, int64_t so_sim_stride,
                                 const int64_t* idx, const float* rescaler, float* state, int64_t B, int F, int nt, int nx, int nt_c,
                                 int nx_c, int kind, int pad_t, int pad_x, wdno_stream_t s);
+/* Dataset packing of the Burgers wavelet models for a batch, one launch (get_wavelet_super_preprocess of burgers/ddpm_burgers/data_burgers_1d.py:
+ * 40-88) that writes every element of
+ *   state[b][c][h][w] = value / rescaler[c],   state [B][C][pad_t][pad_x], C = 8 + 8 has_low + (cond_u0 | cond_uT); everything not listed is 0
+ *   c < 8             : fine[sim][c / 4][c % 4][h][w] for h < nt, w < nx                     (fine [.][2][4][nt][nx]: the sub-bands of u, then of f)
+ *                       has_low: row h == nt repeats row nt - 1 (the reference's "odd number of timesteps" line)
+ *   8 <= c < 16       : has_low: coarse[sim][(c - 8) / 4][(c - 8) % 4][h >> 1][w >> 1] for h < 2 nt_c, w < 2 nx_c   (upsample_coef, not cropped)
+ *   c == C - 1        : cond_u0 | cond_uT: four stripes of pad_t / 4 rows, w < nx -- the low band of u(t = 0), its high band, the low band of
+ *                       u(t = ori_t - 1), its high band: the one-level periodized 1-D analysis along x of that row of u, the row itself
+ *                       synthesised inside the launch from the four sub-bands of u (periodized 2-D synthesis of that output row only). A
+ *                       stripe whose flag is off is zero. The sums run in the order of the transform kernels (wdno_dwt_inv, wdno_dwt_fwd).
+ * sim = idx[b] (device int64; NULL: b); the per-sample strides of the two levels are in elements. dec_* / rec_*: the wavelet's filters, host
+ * arrays of L taps (read only with a condition channel). IEEE division: channels below the condition channel carry the bits of the torch
+ * formulation. Returns, without a launch: WDNO_EINVAL when the box (nt <= pad_t, nx <= pad_x), the repeated row (nt + 1 <= pad_t) or the doubled
+ * coarse block (2 nt_c <= pad_t, 2 nx_c <= pad_x) does not fit, for ori_t outside [1, 2 nt], strides smaller than a sample, flags other than
+ * 0 / 1 or a state that is not 16-byte aligned; WDNO_EUNSUPPORTED unless pad_t % 4 == 0, pad_x % 4 == 0, ori_x == 2 nx, L even and <= 16 (and
+ * pad_t, pad_x <= 4096, B <= 65535). Periodization only. Nothing is allocated. */
+int wdno_pack_burgers_state(const float* fine, int64_t fine_sim_stride, const float* coarse, int64_t coarse_sim_stride, const int64_t* idx,
+                            const float* rescaler, float* state, int64_t B, int nt, int nx, int nt_c, int nx_c, int pad_t, int pad_x,
+                            int ori_t, int ori_x, int has_low, int cond_u0, int cond_uT, const float* dec_lo_host, const float* dec_hi_host,
+                            const float* rec_lo_host, const float* rec_hi_host, int L, wdno_stream_t s);
+/* What that launch does for these integers (nothing is launched, no device is needed; the entry asks the same code): fine_vec / coarse_vec = floats
+ * per load of the fine / coarse rows (4: nx % 4 == 0; 2: even rows; 1 otherwise -- strides and addresses permitting; align_mask: the addresses of
+ * fine | coarse | state OR-ed), the grid (256 threads per block), the dynamic LDS and C. rc = the code the launch would return short of
+ * WDNO_ELAUNCH and the NULL checks; the other fields are 0 then. Returns WDNO_EINVAL only for out == NULL. */
+typedef struct { int fine_vec, coarse_vec, grid_x, grid_y, grid_z, lds_bytes, rc, reserved; } wdno_pack_burgers_plan;
+int wdno_pack_burgers_plan_query(int64_t fine_sim_stride, int64_t coarse_sim_stride, int64_t B, int nt, int nx, int nt_c, int nx_c, int pad_t,
+                                 int pad_x, int ori_t, int ori_x, int has_low, int cond_u0, int cond_uT, int L, unsigned align_mask,
+                                 wdno_pack_burgers_plan* out);
 
 /* ------------------------------------------------------------------------------------------------ layout
  * API layout [N, C, S] (S = product of spatial dims) <-> channels-last [N, S, Cp] (Cp >= C, zero padded). */

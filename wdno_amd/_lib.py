@@ -145,6 +145,10 @@ class BurgersCascadeDesc(C.Structure):      # include/wdno_hip.h: wdno_burgers_c
                                  'cond_u0', 'cond_uT', 'L', 'mode', 'lds_bytes', 'reserved')]
 
 
+class PackBurgersPlan(C.Structure):         # include/wdno_hip.h: wdno_pack_burgers_plan
+    _fields_ = [(k, I) for k in ('fine_vec', 'coarse_vec', 'grid_x', 'grid_y', 'grid_z', 'lds_bytes', 'rc', 'reserved')]
+
+
 class BurgersScoreDesc(C.Structure):        # include/wdno_hip.h: wdno_burgers_score_desc
     _fields_ = [(k, I) for k in ('B', 'n_t', 'n_x', 'sub')] + \
                [(k, C.c_longlong) for k in ('gt_sample_stride', 'gt_row_stride', 'gt_col_stride', 'ut_sample_stride', 'ut_row_stride', 'ut_col_stride')] + \
@@ -171,6 +175,8 @@ PROTOTYPES = {
     'wdno_pack_smoke_state': (I, [P, L, P, L, P, L, P, P, P, L, I, I, I, I, I, P]),
     'wdno_pack_smoke_super_state': (I, [P, L, P, L, P, L, P, L, P, P, P, L, I, I, I, I, I, I, I, I, P]),
     'wdno_pack_smoke_fields': (I, [P, L, P, L, P, L, PF, PF, I, P, P, L, I, I, I, I, I, I, I, I, P]),
+    'wdno_pack_burgers_state': (I, [P, L, P, L, P, P, P, L, I, I, I, I, I, I, I, I, I, I, I, PF, PF, PF, PF, I, P]),
+    'wdno_pack_burgers_plan_query': (I, [L, L, L, I, I, I, I, I, I, I, I, I, I, I, I, C.c_uint, C.POINTER(PackBurgersPlan)]),
     'wdno_nc_to_cl': (I, [P, P, L, I, L, I, P]),
     'wdno_cl_to_nc': (I, [P, P, L, I, L, I, P]),
     'wdno_concat2_cl': (I, [P, I, P, I, P, L, P]),

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libwdno_hip.so')
-SOURCES = ['api.cpp', 'pointwise.hip', 'diffusion.hip', 'pack.hip', 'dwt.hip', 'dwt_analysis.hip', 'dwt_synthesis.hip', 'conv.hip', 'conv_prep.hip', 'conv_h3.hip', 'conv_h3d.hip', 'conv_h3t.hip', 'conv_wgrad_h3.hip', 'conv_wgrad_h3d.hip', 'norm.hip', 'layernorm.hip', 'attention.hip', 'linattn.hip', 'attn_fused.hip', 'attn_fused48.hip', 'attn_fused_wide.hip', 'attn_fused_bwd.hip', 'linattn_fused.hip', 'linattn_fused_wide.hip', 'linattn_fused_bwd.hip', 'linear_rows.hip', 'burgers.hip', 'burgers_datagen.hip', 'burgers_guidance.hip', 'burgers_reconstruct.hip', 'burgers_score.hip', 'burgers_cascade.hip', 'smoke_guidance.hip', 'smoke_reconstruct.hip', 'smoke_score.hip', 'smoke_cascade.hip', 'smoke_solver.hip', 'smoke_datagen.hip']
+SOURCES = ['api.cpp', 'pointwise.hip', 'diffusion.hip', 'pack.hip', 'pack_burgers.hip', 'dwt.hip', 'dwt_analysis.hip', 'dwt_synthesis.hip', 'conv.hip', 'conv_prep.hip', 'conv_h3.hip', 'conv_h3d.hip', 'conv_h3t.hip', 'conv_wgrad_h3.hip', 'conv_wgrad_h3d.hip', 'norm.hip', 'layernorm.hip', 'attention.hip', 'linattn.hip', 'attn_fused.hip', 'attn_fused48.hip', 'attn_fused_wide.hip', 'attn_fused_bwd.hip', 'linattn_fused.hip', 'linattn_fused_wide.hip', 'linattn_fused_bwd.hip', 'linear_rows.hip', 'burgers.hip', 'burgers_datagen.hip', 'burgers_guidance.hip', 'burgers_reconstruct.hip', 'burgers_score.hip', 'burgers_cascade.hip', 'smoke_guidance.hip', 'smoke_reconstruct.hip', 'smoke_score.hip', 'smoke_cascade.hip', 'smoke_solver.hip', 'smoke_datagen.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math']
 RESOURCES = os.path.join(HERE, 'build', 'kernel_resources.json')     # per-kernel registers / scratch from the last build
 

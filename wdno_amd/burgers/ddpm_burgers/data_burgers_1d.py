@@ -8,9 +8,15 @@ of u(t=0) and u(t=T) in four horizontal stripes; everything divided by the per-c
 the physical u: IDWT of the packed coefficients, then a 1-D DWT of two rows -- both run on the GPU here (the reference used
 pytorch_wavelets on whatever device the file was loaded to); the rest is indexing. Results come back on the device of the
 input file, so `DiffusionDataset` / `DataLoader` behave as before.
+
+`pack_burgers_gpu` packs a BATCH of such inputs from coefficient levels resident in HBM in one launch (csrc/pack_burgers.hip: the two
+rows of u behind the condition channel are synthesised inside the launch), `pack_burgers_batch` is the same on tensors of any device;
+wdno_amd.loader.ResidentSuperBurgersLoader feeds the super-resolution trainer with them.
 """
 import math
+import os
 import random
+import weakref
 
 import torch
 from torch import nn
@@ -49,6 +55,35 @@ def _condition_rows(w_uf, shape, ori_shape, mode, wave_type):
     return torch.cat(los), torch.cat(his)
 
 
+def _pack_index(fine, coarse, rescaler, ori_shape, pad_t, pad_x, mode, wave_type, is_condition_u0, is_condition_uT):
+    """The packing as index work on tensors of any device: fine [N, 2, 4, nt, nx], coarse [N, 2, 4, nt_c, nx_c] or None (base models),
+    ori_shape = the level's (ori_t, ori_x) -> [N, C, pad_t, pad_x] / rescaler. The condition rows take _condition_rows' GPU route."""
+    n, nt, nx = fine.size(0), fine.size(-2), fine.size(-1)
+    w_uf = nn.functional.pad(fine.reshape(n, 8, nt, nx), (0, pad_x - nx, 0, pad_t - nt))                # [N, 8, pad, pad]
+    out = w_uf
+    if coarse is not None:
+        sub = _nearest2(coarse.reshape(n, 8, coarse.size(-2), coarse.size(-1)))
+        sub = nn.functional.pad(sub, (0, pad_x - sub.shape[-1], 0, pad_t - sub.shape[-2]))
+        w_uf[:, :, nt, :] = w_uf[:, :, nt - 1, :]            # odd number of time coefficients: repeat the last one
+        out = torch.cat((w_uf, sub), dim=1)
+    if is_condition_u0 or is_condition_uT:
+        lo, hi = _condition_rows(w_uf, (nt, nx), ori_shape, mode, wave_type)
+        cond = torch.zeros_like(out[:, :1])
+        rep = pad_t // 4
+        if is_condition_u0:
+            cond[:, 0, :rep, :nx] = lo[:, None, 0]
+            cond[:, 0, rep:2 * rep, :nx] = hi[:, None, 0]
+        if is_condition_uT:
+            cond[:, 0, 2 * rep:3 * rep, :nx] = lo[:, None, 1]
+            cond[:, 0, 3 * rep:4 * rep, :nx] = hi[:, None, 1]
+        out = torch.cat((out, cond), dim=1)
+    return out / rescaler
+
+
+def level_ori_shape(ori_shape, lvl):
+    return [math.ceil(ori_shape[0] / 2 ** lvl), math.ceil(ori_shape[1] / 2 ** lvl)]
+
+
 def get_wavelet_super_preprocess(rescaler=70, is_super_model=False, N_downsample=0, mode='zero', wave_type='bior2.4',
                                  is_condition_u0=True, is_condition_uT=True):
     if rescaler is None:
@@ -57,34 +92,79 @@ def get_wavelet_super_preprocess(rescaler=70, is_super_model=False, N_downsample
     def preprocess(db):
         lvl = N_downsample if is_super_model else 0
         data = db['coef']
-        w_u, w_f = data[lvl][:, 0][:_MAX_SAMPLES], data[lvl][:, 1][:_MAX_SAMPLES]
-        ori_shape = list(db['ori_shape'])
-        ori_shape[0] = math.ceil(ori_shape[0] / 2 ** lvl)
-        ori_shape[1] = math.ceil(ori_shape[1] / 2 ** lvl)
-        n, nt, nx = w_u.size(0), w_f.size(-2), w_f.size(-1)
-        shape = w_f.shape[2:]
+        fine = data[lvl][:_MAX_SAMPLES]
+        coarse = data[lvl + 1][:_MAX_SAMPLES] if is_super_model else None
+        ori_shape = level_ori_shape(db['ori_shape'], lvl)
         pad_t = pad_x = int(64 / 2 ** lvl)
-        w_uf = nn.functional.pad(torch.cat((w_u, w_f), dim=1), (0, pad_x - nx, 0, pad_t - nt))          # [N, 8, pad, pad]
-        out = w_uf
-        if is_super_model:
-            sub = torch.cat((_nearest2(data[lvl + 1][:, 0][:_MAX_SAMPLES]), _nearest2(data[lvl + 1][:, 1][:_MAX_SAMPLES])), dim=1)
-            sub = nn.functional.pad(sub, (0, pad_x - sub.shape[-1], 0, pad_t - sub.shape[-2]))
-            w_uf[:, :, nt, :] = w_uf[:, :, nt - 1, :]            # odd number of time coefficients: repeat the last one
-            out = torch.cat((w_uf, sub), dim=1)
-        if is_condition_u0 or is_condition_uT:
-            lo, hi = _condition_rows(w_uf, shape, ori_shape, mode, wave_type)
-            cond = torch.zeros_like(out[:, :1])
-            rep = pad_t // 4
-            if is_condition_u0:
-                cond[:, 0, :rep, :nx] = lo[:, None, 0]
-                cond[:, 0, rep:2 * rep, :nx] = hi[:, None, 0]
-            if is_condition_uT:
-                cond[:, 0, 2 * rep:3 * rep, :nx] = lo[:, None, 1]
-                cond[:, 0, 3 * rep:4 * rep, :nx] = hi[:, None, 1]
-            out = torch.cat((out, cond), dim=1)
-        return out / rescaler, list(shape), list(ori_shape)
+        out = _pack_index(fine, coarse, rescaler, ori_shape, pad_t, pad_x, mode, wave_type, is_condition_u0, is_condition_uT)
+        return out, list(fine.shape[-2:]), ori_shape
 
+    # (what a loader needs to pack the same batches itself: wdno_amd.loader.ResidentSuperBurgersLoader, DiffusionDataset's lazy x)
+    preprocess.args = dict(rescaler=rescaler, is_super_model=is_super_model, N_downsample=N_downsample, mode=mode, wave_type=wave_type,
+                           is_condition_u0=is_condition_u0, is_condition_uT=is_condition_uT)
     return preprocess
+
+
+def _rescaler_vector(rescaler, c):
+    r = torch.as_tensor(rescaler, dtype=torch.float32).reshape(-1)
+    if r.numel() == 1:
+        r = r.expand(c)
+    if r.numel() != c:
+        raise ValueError(f'rescaler has {r.numel()} entries, the state {c} channels')
+    return r.contiguous()
+
+
+def pack_burgers_batch(fine, coarse, rescaler, ori_shape, idx=None, pad_t=64, pad_x=64, mode='periodization', wave_type='bior2.4',
+                       is_condition_u0=True, is_condition_uT=True):
+    """get_wavelet_super_preprocess for a batch taken from coefficient levels held on one device: fine [N, 2, 4, nt, nx] (level l), coarse
+    [N, 2, 4, nt_c, nx_c] (level l + 1; None: a base model), ori_shape = level l's field size; idx picks the samples of the batch (None: all, in
+    order) -> [B, 8 + 8 has_low + has_cond, pad_t, pad_x] / rescaler. On CUDA tensors and periodization it is one launch of csrc/pack_burgers.hip
+    (pack_burgers_gpu); otherwise the index formulation of the preprocess on the gathered samples. Both give the same bits in every channel,
+    the condition channel included: the launch keeps the summation order of the transforms behind _condition_rows
+    (tests/test_gpu_burgers_super_loader.py)."""
+    if fine.is_cuda and mode in ('periodization', 'per'):
+        return pack_burgers_gpu(fine, coarse, rescaler, ori_shape, idx, pad_t, pad_x, wave_type, is_condition_u0, is_condition_uT)
+    if idx is not None:
+        idx = torch.as_tensor(idx, dtype=torch.int64, device=fine.device)
+        fine = fine.index_select(0, idx)
+        coarse = None if coarse is None else coarse.index_select(0, idx)
+    c = 8 + (8 if coarse is not None else 0) + (1 if (is_condition_u0 or is_condition_uT) else 0)
+    r = _rescaler_vector(rescaler, c).to(fine.device).reshape(1, c, 1, 1)
+    return _pack_index(fine, coarse, r, list(ori_shape), pad_t, pad_x, mode, wave_type, is_condition_u0, is_condition_uT)
+
+
+_taps = {}
+
+
+def pack_burgers_gpu(fine, coarse, rescaler, ori_shape, idx=None, pad_t=64, pad_x=64, wave_type='bior2.4', is_condition_u0=True,
+                     is_condition_uT=True):
+    """wdno_pack_burgers_state (csrc/pack_burgers.hip): the states of a batch in one launch from device-resident coefficient levels, periodization
+    mode. Arguments as pack_burgers_batch; idx is an int64 device tensor [B]. The shape rules are the library's (include/wdno_hip.h)."""
+    import ctypes as C
+    from wdno_amd import _lib
+    from wdno_amd.filters import filter_bank
+    from wdno_amd.ops import _lib_, _p, _stream
+    for t, name in ((fine, 'fine'), (coarse, 'coarse')):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError(f'wdno_amd pack_burgers_gpu: {name} must be a contiguous float32 tensor on the GPU')
+    n, nt, nx = fine.shape[0], fine.shape[-2], fine.shape[-1]
+    assert tuple(fine.shape[1:3]) == (2, 4) and (coarse is None or tuple(coarse.shape[:3]) == (n, 2, 4))
+    nt_c, nx_c = (coarse.shape[-2], coarse.shape[-1]) if coarse is not None else (0, 0)
+    c = 8 + (8 if coarse is not None else 0) + (1 if (is_condition_u0 or is_condition_uT) else 0)
+    r = _rescaler_vector(rescaler, c).to(fine.device)
+    taps = _taps.get(wave_type)
+    if taps is None:
+        taps = _taps[wave_type] = tuple((C.c_float * len(bank))(*[float(v) for v in bank]) for bank in filter_bank(wave_type))
+    if idx is not None:
+        idx = idx.to(device=fine.device, dtype=torch.int64).contiguous()
+    b = n if idx is None else idx.numel()
+    with torch.cuda.device(fine.device):
+        out = torch.empty((b, c, pad_t, pad_x), device=fine.device, dtype=torch.float32)
+        _lib.check(_lib_().wdno_pack_burgers_state(_p(fine), fine[0].numel(), _p(coarse), 0 if coarse is None else coarse[0].numel(), _p(idx), _p(r),
+                                                   _p(out), b, nt, nx, nt_c, nx_c, pad_t, pad_x, int(ori_shape[0]), int(ori_shape[1]),
+                                                   int(coarse is not None), int(bool(is_condition_u0)), int(bool(is_condition_uT)), *taps,
+                                                   len(taps[0]), _stream()), 'pack_burgers_state')
+    return out
 
 
 def get_burgers_preprocess(rescaler=10, is_super_model_train=False, N_downsample=0, is_super_model_test=False, upsample_t=0, upsample_x=0):
@@ -128,13 +208,56 @@ def get_wavelet_preprocess(rescaler=70, mode='zero', wave_type='bior2.4', is_con
     return preprocess
 
 
+class _FileDict(dict):
+    """A file's dictionary that can be referenced weakly and remembers the mtime it was read at"""
+    mtime = None
+
+
+_files = weakref.WeakValueDictionary()     # path -> the file's dictionary, for as long as a dataset holds it: the level datasets of one
+                                           # coefficient file share one read, and nothing stays in host memory after the last of them is gone
+
+
+def _read_file(fname):
+    path = os.path.abspath(fname)
+    mtime = os.path.getmtime(path)
+    held = _files.get(path)
+    if held is None or held.mtime != mtime:
+        held = _FileDict(torch.load(path, weights_only=False))
+        held.mtime = mtime
+        _files[path] = held
+    return held
+
+
 class DiffusionDataset(Dataset):
+    """x [N, C, pad, pad]: the packed tensor of the whole file, built by `preprocess` in the constructor. With the preprocess of a
+    super-resolution level (get_wavelet_super_preprocess(is_super_model=True)) shape, ori_shape and the length come from the file's metadata
+    and x is built on its first use (`x`, `ds[i]`) -- a loader that packs batches from the coefficient levels themselves
+    (wdno_amd.loader.ResidentSuperBurgersLoader) never builds it. The first use must happen in the process that owns the dataset:
+    DataLoader workers would each build a copy of their own."""
+
     def __init__(self, fname, preprocess=None):
-        self.db = torch.load(fname, weights_only=False) if isinstance(fname, str) else fname
-        self.x, self.shape, self.ori_shape = (preprocess or get_wavelet_preprocess())(self.db)
+        self.db = _read_file(fname) if isinstance(fname, str) else fname
+        self.preprocess = preprocess or get_wavelet_preprocess()
+        a = getattr(self.preprocess, 'args', None)
+        if a is not None and a['is_super_model']:
+            fine = self.db['coef'][a['N_downsample']]
+            self._x, self._len = None, min(fine.shape[0], _MAX_SAMPLES)
+            self.shape, self.ori_shape = list(fine.shape[-2:]), level_ori_shape(self.db['ori_shape'], a['N_downsample'])
+        else:
+            self._x, self.shape, self.ori_shape = self.preprocess(self.db)
+            self._len = self._x.size(0)
+
+    @property
+    def x(self):
+        if self._x is None:
+            if torch.utils.data.get_worker_info() is not None:
+                raise RuntimeError('DiffusionDataset: x of a super-resolution level is built on first use, and this is a DataLoader worker: '
+                                   'touch `dataset.x` in the parent process before the workers start (SuperDataLoader does)')
+            self._x = self.preprocess(self.db)[0]
+        return self._x
 
     def __len__(self):
-        return self.x.size(0)
+        return self._len
 
     def __getitem__(self, idx):
         return self.x[idx]
@@ -153,6 +276,8 @@ class SuperDataLoader:
         """seed (an extension): private shuffle / level-choice streams, e.g. base + 1000 * rank under data parallelism -- the
         reference's loader is not sharded by accelerate, and identically seeded ranks would draw identical batches."""
         self.dataset = dataset
+        for ds in dataset:                # a level's packed tensor is built on first use: here, not once in every worker process
+            getattr(ds, 'x', None)
         gens = [None if seed is None else torch.Generator().manual_seed(seed + i) for i in range(len(dataset))]
         self.dl = [cycle(DataLoader(ds, batch_size=batch_size, shuffle=shuffle, pin_memory=pin_memory, num_workers=num_workers, generator=g))
                    for ds, g in zip(dataset, gens)]

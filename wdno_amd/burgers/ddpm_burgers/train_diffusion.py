@@ -68,9 +68,33 @@ class Trainer(TrainerCore):
             dl = self.make_loader(dataset, self.local_batch_size, workers)
         else:                                      # a list of datasets, one group drawn at random per batch (data_burgers_1d.py SuperDataLoader)
             from ddpm_burgers.data_burgers_1d import SuperDataLoader
-            dl = SuperDataLoader(dataset, batch_size=self.local_batch_size, shuffle=True, pin_memory=True, num_workers=workers,
-                                 seed=self.data_seed if self.world > 1 else None)
+            # the coefficient levels in HBM, every batch packed on the GPU (wdno_amd.loader.ResidentSuperBurgersLoader) where that serves
+            dl = self.make_super_burgers_loader(dataset, self.local_batch_size)
+            if dl is None:
+                dl = SuperDataLoader(dataset, batch_size=self.local_batch_size, shuffle=True, pin_memory=True, num_workers=workers,
+                                     seed=self.data_seed if self.world > 1 else None)
+        self.loader = dl                  # what feeds the steps (tests, diagnostics)
         self.dl = self.cycle(dl)          # advances DistributedSampler epochs
+
+    def make_super_burgers_loader(self, datasets, batch_size):
+        """The resident pipeline for the list of level datasets of the super-resolution model, or None where SuperDataLoader has to serve:
+        resident_data off, a list that is not the levels 0 .. N - 1 of one coefficient file (load_super_model's [base dataset], for one), a mode
+        other than periodization, or levels that would take half of the free HBM or more (TrainerCore.make_super_loader's rule)."""
+        from wdno_amd import loader as L
+        if not self.resident_data:
+            return None
+        try:
+            levels = L.ResidentSuperBurgersLoader.levels_of(datasets)
+        except ValueError:
+            return None
+        if datasets[0].preprocess.args['mode'] not in ('periodization', 'per'):
+            return None
+        if 4 * sum(t.numel() for t in levels) >= torch.cuda.mem_get_info(self._device)[0] // 2:
+            return None
+        # ranks agree on the per-level permutations (the shards of an epoch are disjoint) and, by a common level seed, on the level of every step
+        order_seed = 0 if self.world > 1 else int(torch.empty((), dtype=torch.int64).random_().item())
+        return L.ResidentSuperBurgersLoader(datasets, batch_size, self._device, True, self.rank, self.world, seed=1234 if self.world > 1 else None,
+                                            order_seed=order_seed)
 
     def _path(self, milestone):
         if type(milestone) is int:

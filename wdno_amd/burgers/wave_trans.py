@@ -53,3 +53,38 @@ def transform_dataset(data, wave_type='bior2.4', mode='periodization', N_downsam
     from wdno_amd import wavelets as W
     coef = [W.dwt_packed(data[:, :, ::2 ** i, ::2 ** i].contiguous(), wave_type, mode, 2).cpu() for i in range(N_downsample)]
     return {'coef': coef, 'shape': [c.shape[2:] for c in coef], 'ori_shape': data.shape[2:]}
+
+
+def write_coef_file(train_path, out_path, wave_type='bior2.4', mode='periodization', N_downsample=4, batch_size=20000):
+    """The script body of wave_trans.py:66-124: the training set {'u': [N, nt + 1, nx], 'f': [N, nt, nx]} -> the coefficient file
+    train_ddpm_burgers.py reads. f gets its zero last row, (u, f) go through transform_dataset in chunks of batch_size samples (each chunk
+    up to the GPU and back once, as the reference's DataLoader does). Returns the dictionary it saved."""
+    all_data = torch.load(train_path, weights_only=False)
+    u, f = all_data['u'].float(), all_data['f'].float()
+    f = torch.cat((f, torch.zeros(f.shape[0], 1, f.shape[-1])), dim=1)
+    data = torch.stack((u, f), dim=1)                                    # [N, 2, nt + 1, nx]
+    parts = [transform_dataset(data[a:a + batch_size].cuda(), wave_type, mode, N_downsample) for a in range(0, data.shape[0], batch_size)]
+    out = {'coef': [torch.cat([p['coef'][i] for p in parts]) for i in range(N_downsample)], 'shape': parts[0]['shape'],
+           'ori_shape': data.shape[2:]}
+    torch.save(out, out_path)
+    return out
+
+
+def report(out):
+    """One line per coefficient level: its tensor's shape and the largest magnitude in each of the eight sub-bands (u's four, then f's),
+    the numbers the per-channel RESCALER of the trainers is read from."""
+    lines = []
+    for lvl, coef in enumerate(out['coef']):
+        peaks = coef.abs().amax(dim=(0, 3, 4)).reshape(-1).tolist()
+        lines.append(f'level {lvl}: {tuple(coef.shape)}  |band| max  u ' + ' '.join(f'{v:.3f}' for v in peaks[:4]) +
+                     '  f ' + ' '.join(f'{v:.3f}' for v in peaks[4:]))
+    return lines
+
+
+if __name__ == '__main__':
+    import time
+    t0 = time.perf_counter()
+    target = 'data/1d/coef_bior2.4_periodization_super'
+    written = write_coef_file('data/1d/train', target, 'bior2.4', 'periodization', N_downsample=4)
+    print('\n'.join(report(written)))
+    print(f'wrote {target} in {time.perf_counter() - t0:.1f} s')

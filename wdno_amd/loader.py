@@ -12,6 +12,9 @@ HBM: the whole training set (smoke: 20 000 simulations x 3.35 MB of raw coeffici
   * ResidentSuperSmokeLoader : the same for the list of level datasets of a super-resolution smoke model (SuperDataLoader's contract: one batch of
                            one randomly chosen level per iteration): one set of stores per coefficient level, each file read once for all levels,
                            every two-level batch packed by wdno_pack_smoke_super_state.
+  * ResidentSuperBurgersLoader : the same contract for the level datasets of the Burgers super-resolution model: the coefficient levels of the one
+                           file live in HBM once each, every batch is one launch of wdno_pack_burgers_state (csrc/pack_burgers.hip), condition
+                           channel included; the packed host tensors of the levels are never built.
 
 The first two iterate like `DataLoader(dataset, batch_size, shuffle=True, drop_last=False)` under a DistributedSampler (rank-disjoint shards of a padded
 per-epoch permutation, reshuffled every epoch by `set_epoch`), yield DEVICE tensors, and are what the drop-in Trainers use when
@@ -251,3 +254,74 @@ class ResidentSuperSmokeLoader:
         pad_t, pad_x = self.pads(lvl)
         state = pack_smoke_super_batch(self.coef[lvl], self.coef[lvl + 1], self.init[lvl], self.so[lvl], self.rescaler[lvl], self.kind, idx, pad_t, pad_x)
         yield state, list(self.coef[lvl].shape[-3:]), None, torch.tensor(ids)
+
+
+class ResidentSuperBurgersLoader:
+    """`SuperDataLoader([DiffusionDataset(file, get_wavelet_super_preprocess(is_super_model=True, N_downsample=i)) for i < N], batch_size)` with the
+    coefficient levels resident in HBM: every `__iter__` yields ONE batch of one randomly chosen level, a device tensor [B, C, pad, pad] with
+    pad = 64 / 2^level, packed by one launch of wdno_pack_burgers_state (csrc/pack_burgers.hip) with an index list. The datasets' packed host
+    tensors (DiffusionDataset.x: 11.1 + 2.8 + 0.7 GB for 40 000 samples and three levels) are never built.
+
+    Levels 0 .. N are uploaded once each at construction; level i + 1 is dataset i's coarse level and dataset i + 1's fine level. Each level has
+    its own _EpochOrder (seed `order_seed` + level, sharded by rank / world like a DistributedSampler), cursor and epoch counter; the short last
+    batch of a level's epoch is kept. `seed` (None: the global `random`) makes the level choice a private random.Random(seed), as
+    SuperDataLoader's does. device='cpu' packs the same batches through the index formulation (ddpm_burgers.data_burgers_1d.pack_burgers_batch)."""
+
+    def __init__(self, datasets, batch_size, device, shuffle=True, rank=0, world=1, seed=None, order_seed=0):
+        import random
+        from ddpm_burgers.data_burgers_1d import _rescaler_vector, level_ori_shape
+        levels = self.levels_of(datasets)
+        self.ds, self.batch_size, self.device = list(datasets), batch_size, torch.device(device)
+        self.args = [d.preprocess.args for d in self.ds]
+        self.coef = [lv.to(device=self.device, dtype=torch.float32).contiguous() for lv in levels]
+        self.ori_shape = [level_ori_shape(self.ds[0].db['ori_shape'], lvl) for lvl in range(len(self.ds))]
+        c = 16 + (1 if (self.args[0]['is_condition_u0'] or self.args[0]['is_condition_uT']) else 0)
+        self.rescaler = [_rescaler_vector(a['rescaler'], c).to(self.device) for a in self.args]          # (uploaded once, not per batch)
+        n = self.coef[0].shape[0]
+        self.samplers = [_EpochOrder(n, rank, world, shuffle, order_seed + lvl) for lvl in range(len(self.ds))]
+        self.epoch = [0] * len(self.ds)
+        self._order = [None] * len(self.ds)
+        self._order_dev = [None] * len(self.ds)          # the epoch's order on the device: one small upload per level and epoch, none per batch
+        self._cursor = [0] * len(self.ds)
+        self._rng = random if seed is None else random.Random(seed)
+
+    @staticmethod
+    def levels_of(datasets):
+        """The coefficient levels 0 .. N of a list of level datasets (host tensors, cut to the datasets' length), or ValueError unless the list is
+        the levels 0 .. N - 1 of one file with one set of condition flags."""
+        datasets = list(datasets)
+        args = [getattr(getattr(d, 'preprocess', None), 'args', None) for d in datasets]
+        if not datasets or not all(a is not None and a['is_super_model'] for a in args):
+            raise ValueError('ResidentSuperBurgersLoader serves a list of DiffusionDatasets built with get_wavelet_super_preprocess(is_super_model=True)')
+        if [a['N_downsample'] for a in args] != list(range(len(datasets))) or any(d.db is not datasets[0].db for d in datasets):
+            raise ValueError('ResidentSuperBurgersLoader: the datasets must be the levels 0 .. N - 1 of one coefficient file')
+        if len({(a['mode'], a['wave_type'], bool(a['is_condition_u0']), bool(a['is_condition_uT'])) for a in args}) != 1:
+            raise ValueError('ResidentSuperBurgersLoader: the levels must share the wavelet, the mode and the condition flags')
+        coef = datasets[0].db['coef']
+        if len(coef) < len(datasets) + 1:
+            raise ValueError(f'ResidentSuperBurgersLoader: {len(datasets)} levels need {len(datasets) + 1} coefficient levels, the file has {len(coef)}')
+        return [coef[lvl][:len(datasets[0])] for lvl in range(len(datasets) + 1)]
+
+    def resident_bytes(self):
+        return 4 * sum(t.numel() for t in self.coef)
+
+    def __len__(self):
+        return len(self.ds) * math.ceil(len(self.samplers[0].indices()) / self.batch_size)
+
+    def __iter__(self):
+        from ddpm_burgers.data_burgers_1d import pack_burgers_batch
+        lvl = self._rng.randint(0, len(self.ds) - 1)
+        if self._order[lvl] is None or self._cursor[lvl] >= len(self._order[lvl]):
+            if self._order[lvl] is not None:
+                self.epoch[lvl] += 1
+            self.samplers[lvl].set_epoch(self.epoch[lvl])
+            self._order[lvl], self._cursor[lvl] = self.samplers[lvl].indices(), 0
+            self._order_dev[lvl] = torch.tensor(self._order[lvl], dtype=torch.int64).to(self.device)
+        k = self._cursor[lvl]
+        ids = self._order[lvl][k:k + self.batch_size]
+        idx = self._order_dev[lvl][k:k + self.batch_size]
+        self._cursor[lvl] += len(ids)
+        self.last_ids = (lvl, ids)                          # (tests / diagnostics: SuperDataLoader's batches carry no sample ids either)
+        a, pad = self.args[lvl], 64 // 2 ** lvl
+        yield pack_burgers_batch(self.coef[lvl], self.coef[lvl + 1], self.rescaler[lvl], self.ori_shape[lvl], idx, pad, pad, a['mode'], a['wave_type'],
+                                 a['is_condition_u0'], a['is_condition_uT'])

@@ -2357,6 +2357,22 @@ def dwt_plan(kind, nd, mode, L, n_img, in_dims, out_dims, cs):
     return out
 
 
+def pack_burgers_plan(nt, nx, nt_c, nx_c, pad_t, pad_x, ori_t, ori_x, has_low=True, cond_u0=True, cond_uT=True, L=10, B=1, fine_stride=None,
+                      coarse_stride=None, align_mask=0):
+    """What wdno_pack_burgers_state launches for these integers (csrc/pack_burgers.hip: wdno_pack_burgers_plan_query): dict(fine_vec, coarse_vec
+    -- floats per load of the fine / coarse rows --, grid_x, grid_y, grid_z, lds_bytes, rc). Strides default to contiguous samples. No launch, no
+    device needed."""
+    pl = _lib.PackBurgersPlan()
+    fs = 8 * nt * nx if fine_stride is None else fine_stride
+    cs = 8 * nt_c * nx_c if coarse_stride is None else coarse_stride
+    _lib.check(_lib_().wdno_pack_burgers_plan_query(int(fs), int(cs), int(B), int(nt), int(nx), int(nt_c), int(nx_c), int(pad_t), int(pad_x), int(ori_t),
+                                                    int(ori_x), int(bool(has_low)), int(bool(cond_u0)), int(bool(cond_uT)), int(L),
+                                                    int(align_mask) & 0xffffffff, C.byref(pl)), 'pack_burgers_plan')
+    out = _plan_dict(pl)
+    out.pop('reserved')
+    return out
+
+
 def upsample_coef_raw(x, outer, a, mid, b, c, fa, fb, fc):
     x = _chk(x, 'coef')
     out = torch.empty((outer * a * fa * mid * b * fb * c * fc,), device=x.device, dtype=torch.float32)
